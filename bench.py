@@ -1,16 +1,26 @@
 #!/usr/bin/env python
 """Benchmark of the SEGAN+ GAN training step on MI355X (BASELINE.json's metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one full LSGAN step of the reference's ``SEGAN.train`` inner loop
 (segan/models/model.py:292-321: G fwd, D fwd real+fake, D bwd, D step, D fwd on fake,
 G bwd + L1, G step) on a batch of 300 synthetic 16384-sample noisy/clean pairs PER GPU
 (BASELINE.json configs[1]: SEGAN+ default net, k31, batch 300, fp32), inputs resident
 in HBM before the timed region, no logging syncs inside it.  With N > 1 there is one rank per
-GPU: when the driver has not launched the ranks itself (WORLD_SIZE unset) the script re-executes
-under ``python -m torch.distributed.run --nproc-per-node N``; the batch is sharded 300/GPU
+GPU: when the driver has not launched the ranks itself (WORLD_SIZE unset) the script runs itself as
+a child under ``python -m torch.distributed.run --nproc-per-node N``; the batch is sharded 300/GPU
 (weak scaling) and gradients are averaged by RCCL all-reduces on the flat gradient arenas.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step and
+what describes them).  --dump-outputs DIR writes what the last timed step computed as DIR/*.npy
+(float32): the losses the step returns and a fixed, seeded sample of each network's state after it.
+The inputs are the same in every run; in the default reduction mode (fp32 atomics) the dumped values
+still differ from run to run by the summation order, compounded over the W + K steps, and
+SEGAN_DETERMINISTIC=1 selects the fixed-order reductions.
+Everything below that is not the headline — the kernel timer's roofline blocks, host costs, the other
+reduction modes, precisions and workloads, the CPU baseline with its parity legs, the multi-GPU
+communication statistics — runs with --full only (the --no-* options trim a --full run).
 
 Prints ONE JSON line (rank 0):
   value       whole-job 16384-sample chunks/s
@@ -694,6 +704,27 @@ def make_workload(shape, wsegan, dev, rank, B, device_z=False):
                            shape=shape, wsegan=wsegan)
 
 
+DUMP_SAMPLE = 1 << 20     # elements of each network's state written by --dump-outputs
+
+
+def dump_outputs(path, w, step_out):
+    """--dump-outputs: what the timed path computed in its last step, as float32 .npy files under
+    `path` — the four losses the step returned and, per network, the same seeded sample of its state
+    after the step (the floating-point state_dict entries flattened in order: weights, BatchNorm
+    statistics)."""
+    os.makedirs(path, exist_ok=True)
+    names = (('d_loss', 'g_cost', 'pow_loss', 'den_loss') if w.wsegan else
+             ('d_real_loss', 'd_fake_loss', 'g_adv_loss', 'g_l1_loss'))
+    for name, t in zip(names, step_out):
+        np.save(os.path.join(path, name + '.npy'), t.detach().float().cpu().numpy())
+    for tag, net in (('G', w.model.G), ('D', w.model.D)):
+        flat = torch.cat([v.detach().reshape(-1).float() for v in net.state_dict().values()
+                          if v.is_floating_point()])
+        idx = np.random.default_rng(0).choice(flat.numel(), min(DUMP_SAMPLE, flat.numel()), replace=False)
+        idx = torch.from_numpy(np.sort(idx)).to(flat.device)
+        np.save(os.path.join(path, tag + '_state_sample.npy'), flat[idx].cpu().numpy())
+
+
 def measure_host(one_step, reps=5):
     """What the HOST side of a step costs, and what the GPU side costs when the host is never the one
     being waited for (round-5 review, weak 4 / next 3c):
@@ -838,7 +869,7 @@ def main():
     ap.add_argument('--no-modes', action='store_true', help='skip the bf16x3 / bf16 side measurements')
     ap.add_argument('--no-side-workloads', action='store_true',
                     help='skip the `other_workloads` block (WSEGAN = BASELINE config 4, the 11-layer stride-2 '
-                         'shape = config 2 as worded) that the default fp32 SEGAN+ run carries')
+                         'shape = config 2 as worded) that a --full fp32 SEGAN+ run carries')
     ap.add_argument('--side-steps', type=int, default=10, help='timed steps per side workload')
     ap.add_argument('--no-host-measure', action='store_true',
                     help='skip measure_host (host enqueue time per step, GPU time of an unstarved step)')
@@ -857,7 +888,20 @@ def main():
                     help='forward/data-gradient contraction precision (default: exact fp32, the '
                          'BASELINE configuration; bf16x3 = exact 3-way bf16 split of fp32 operands; '
                          'bf16 = BASELINE config 5)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed step computed to DIR/*.npy (float32)')
+    ap.add_argument('--full', action='store_true',
+                    help='measure and check everything beside the headline as well: kernel timer and '
+                         'roofline blocks, host costs, the other reduction modes / precisions / '
+                         'workloads, the CPU baseline and its parity legs, multi-GPU communication '
+                         'statistics (the --no-* options trim it)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if not args.full:
+        # a plain run does only what the headline needs
+        args.no_kernel_timer = args.no_host_measure = args.no_modes = True
+        args.no_side_workloads = args.no_cpu_baseline = True
 
     # one rank per GPU: when nobody launched the ranks for us, do it ourselves
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -871,7 +915,9 @@ def main():
                '--nproc-per-node', str(args.gpus), '--master-addr', '127.0.0.1',
                '--master-port', str(port), os.path.abspath(__file__)] + sys.argv[1:]
         os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
-        os.execvp(cmd[0], cmd)
+        # a child process, not exec: this process has already initialised the GPU runtime
+        import subprocess
+        raise SystemExit(subprocess.call(cmd))
 
     from segan_pytorch_amd import distributed as sdist
     from segan_pytorch_amd import losses
@@ -919,9 +965,10 @@ def main():
         timer = KernelTimer()
         timer.install()
         timer.active = False
-    # world > 1: two event records per optimizer step of the TIMED steps (comm_stats below)
+    # --full at world > 1: two event records per optimizer step of the TIMED steps (comm_stats below)
+    comm_stats = world > 1 and args.full
     dt, losses_out = run_timed(one_step, args.steps, args.warmup, barrier, timer,
-                               on_timed_start=(lambda: sdist.set_profile(True)) if world > 1 else None)
+                               on_timed_start=(lambda: sdist.set_profile(True)) if comm_stats else None)
     if timer is not None:
         timer.uninstall()
     if world > 1:
@@ -932,6 +979,8 @@ def main():
     # peak device memory of the warm-up + timed steps (no cyclic collection runs inside the timed region:
     # the step must not depend on the collector to release its activations)
     peak_gb = torch.cuda.max_memory_allocated(dev) / 2 ** 30
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wl, losses_out)
     if timer is not None and timer.sampled > 0:
         # what the engine EXECUTED, from the FLOPs the timed launches were booked with (round-5 review,
         # weak 7: the formula's "one D forward less" missed the skipped z half of dec0's data gradient
@@ -947,7 +996,7 @@ def main():
     # ---- the first multi-GPU run diagnoses itself (round-3 review, item 6): what the gradient
     # exchange cost in the timed steps, and the same steps with the OTHER transport ----
     comm = None
-    if world > 1:
+    if comm_stats:
         comm = sdist.comm_stats()
         sdist.set_profile(False)
         for a in comm['arenas']:

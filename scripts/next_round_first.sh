@@ -5,7 +5,7 @@ set -u
 R=${1:-r06}
 cd $GRAFT_REPO_ROOT; O=gpurun_out/${R}_first; mkdir -p $O
 # headline + deterministic + blocked + bf16x3 + bf16 legs, no CPU oracle (that is 3 of a default run's 4 minutes)
-python bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err
+python bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err
 # what the LDS-fed bf16 MFMA loop sustains per wave-tile shape (first row)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -o scripts/bf16_tile_probe scripts/bf16_tile_probe.hip 2> $O/probe_build.err \
   && timeout 60 scripts/bf16_tile_probe > $O/bf16_tile_probe.json 2> $O/probe.err

@@ -7,6 +7,6 @@ for p in bf16 bf16x3; do
 done
 SEGAN_PRECISION=bf16 python scripts/bench_layers.py --iters 3 > $O/layers_bf16.txt 2>&1
 SEGAN_PRECISION=bf16x3 python scripts/bench_layers.py --iters 3 > $O/layers_bf16x3.txt 2>&1
-SEGAN_DETERMINISTIC=1 python bench.py --steps 10 --warmup 3 --no-modes --no-cpu-baseline > $O/bench_det.json 2>$O/bench_det.err
-python bench.py --steps 10 --warmup 3 --no-modes --no-cpu-baseline > $O/bench_fp32.json 2>$O/bench_fp32.err
+SEGAN_DETERMINISTIC=1 python bench.py --full --steps 10 --warmup 3 --no-modes --no-cpu-baseline > $O/bench_det.json 2>$O/bench_det.err
+python bench.py --full --steps 10 --warmup 3 --no-modes --no-cpu-baseline > $O/bench_fp32.json 2>$O/bench_fp32.err
 tail -2 $O/layers_bf16.txt; cut -c1-300 $O/bench_det.json; cut -c1-300 $O/bench_fp32.json

@@ -12,8 +12,8 @@ cp $O/pmc_hbm_traffic_vanilla11.json profiles/r05_pmc_hbm_traffic_vanilla11.json
 cp $O/sq_counters_fp32.json profiles/r05_sq_counters.json; cp $O/sq_counters_bf16.json profiles/r05_sq_counters_bf16.json
 cp $O/layers_fp32.txt profiles/r05_layers.txt; cp $O/layers_bf16.txt profiles/r05_layers_bf16.txt
 F=gpurun_out/r05f; mkdir -p $F
-python bench.py > $F/bench_line.json 2> $F/bench_line.err
-python bench.py --wsegan --no-modes > $F/bench_line_wsegan.json 2> $F/bench_line_wsegan.err
-python bench.py --shape vanilla11 --no-modes --no-cpu-baseline > $F/bench_line_vanilla11.json 2> /dev/null
+python bench.py --full > $F/bench_line.json 2> $F/bench_line.err
+python bench.py --full --wsegan --no-modes > $F/bench_line_wsegan.json 2> $F/bench_line_wsegan.err
+python bench.py --full --shape vanilla11 --no-modes --no-cpu-baseline > $F/bench_line_vanilla11.json 2> /dev/null
 python scripts/train_loop_bench.py --items 30000 --epochs 3 2>/dev/null | tail -1 > $F/train_loop.json
 cut -c1-400 $F/bench_line.json; cut -c1-300 $F/bench_line_wsegan.json; cut -c1-300 $F/bench_line_vanilla11.json; cat $F/train_loop.json

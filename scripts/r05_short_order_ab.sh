@@ -7,7 +7,7 @@ set -u
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r05_short_ab; rm -rf $O; mkdir -p $O
 for v in 1 0 1 0; do
-  SEGAN_SHORT_ORDER=$v python bench.py --no-modes --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null \
+  SEGAN_SHORT_ORDER=$v python bench.py --full --no-modes --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null \
     | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(json.dumps({'order': $v, 'ms_per_step': d['ms_per_step'], 'corr_frac': d['roofline']['frac']}))" >> $O/steps.jsonl
 done
 for v in 1 0; do

@@ -7,6 +7,6 @@ python scripts/bench_layers.py --iters 7 --only enc0 2>/dev/null | cut -c1-80
 python scripts/bench_layers.py --iters 7 --only dec4 2>/dev/null | cut -c1-80
 python scripts/bench_layers.py --shape vanilla11 --iters 7 --only enc0 2>/dev/null | cut -c1-80
 python scripts/bench_layers.py --shape vanilla11 --iters 7 --only dec10 2>/dev/null | cut -c1-80
-python bench.py --no-cpu-baseline --no-modes --no-host-measure 2>/dev/null | python -c "
+python bench.py --full --no-cpu-baseline --no-modes --no-host-measure 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); print('step', round(d['ms_per_step'],3), {k:round(v['ms_per_step'],2) for k,v in d['other_workloads'].items() if k!='note'})"

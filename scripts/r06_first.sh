@@ -10,5 +10,5 @@ for a in "--shape segan_plus" "--shape vanilla11" "--wsegan"; do
 done
 python scripts/host_profile.py --wsegan --no-prefetch --cprofile 0 > $O/host_wsegan_noprefetch.txt 2>&1
 python scripts/bench_layers.py --shape vanilla11 --iters 3 --verbose > $O/layers_vanilla11.txt 2>&1
-( time python bench.py ) > $O/bench_default.log 2>&1
+( time python bench.py --full ) > $O/bench_default.log 2>&1
 tail -c 600 $O/tests_new.log; head -c 1500 $O/host_shapevanilla11.txt

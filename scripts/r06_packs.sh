@@ -8,6 +8,6 @@ for p in fp32 bf16; do
   python scripts/rocpd_stats.py $O/prof_$p/*results.db $O/kernel_stats_$p.csv 7 > /dev/null 2>&1; rm -rf $O/prof_$p
 done
 tail -3 $O/tests.log; grep -E "pack_" $O/kernel_stats_fp32.csv $O/kernel_stats_bf16.csv | cut -c1-200
-python bench.py --no-cpu-baseline --no-side-workloads 2>/dev/null | python -c "
+python bench.py --full --no-cpu-baseline --no-side-workloads 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); print(d['value'], d['ms_per_step'], {k:v['ms_per_step'] for k,v in d['other_precisions'].items() if k!='note'})"

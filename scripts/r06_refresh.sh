@@ -26,9 +26,9 @@ cp $O/sq_counters_fp32.json $P/${R}_sq_counters.json; cp $O/sq_counters_bf16.jso
 cp $O/layers_fp32.txt $P/${R}_layers.txt; cp $O/layers_bf16.txt $P/${R}_layers_bf16.txt; cp $O/layers_vanilla11.txt $P/${R}_layers_vanilla11.txt
 F=gpurun_out/${R}f; mkdir -p $F
 cp $P/${R}_*.csv $P/${R}_pmc*.json $P/${R}_sq*.json $P/${R}_layers*.txt $F/ 2>/dev/null
-( time python bench.py ) > $F/bench_line.json 2> $F/bench_line.err
-python bench.py --wsegan --no-modes --no-side-workloads > $F/bench_line_wsegan.json 2> $F/bench_line_wsegan.err
-python bench.py --shape vanilla11 --no-modes --no-cpu-baseline > $F/bench_line_vanilla11.json 2> /dev/null
-python bench.py --precision bf16 --device-z --no-modes --no-cpu-baseline --no-side-workloads > $F/bench_line_bf16.json 2> /dev/null
+( time python bench.py --full ) > $F/bench_line.json 2> $F/bench_line.err
+python bench.py --full --wsegan --no-modes --no-side-workloads > $F/bench_line_wsegan.json 2> $F/bench_line_wsegan.err
+python bench.py --full --shape vanilla11 --no-modes --no-cpu-baseline > $F/bench_line_vanilla11.json 2> /dev/null
+python bench.py --full --precision bf16 --device-z --no-modes --no-cpu-baseline --no-side-workloads > $F/bench_line_bf16.json 2> /dev/null
 python scripts/train_loop_bench.py --items 30000 --epochs 3 2>/dev/null | tail -1 > $F/train_loop.json
 cut -c1-300 $F/bench_line.json; tail -4 $F/bench_line.err; cut -c1-200 $F/bench_line_wsegan.json; cut -c1-200 $F/bench_line_vanilla11.json; cut -c1-200 $F/bench_line_bf16.json; cat $F/train_loop.json

@@ -8,7 +8,7 @@ for w in 0 1 0 1; do
   echo "wide=$w"; grep -E "enc[1-3] dgrad" $O/layers_w$w.txt | cut -c1-80
   SEGAN_T_WIDE=$w python scripts/bench_layers.py --shape vanilla11 --iters 5 --only dec > $O/layersd_w$w.txt 2>&1
   grep -E "dec[789] fwd" $O/layersd_w$w.txt | cut -c1-80
-  SEGAN_T_WIDE=$w python bench.py --shape vanilla11 --no-cpu-baseline --no-modes --no-host-measure 2>/dev/null | python -c "
+  SEGAN_T_WIDE=$w python bench.py --full --shape vanilla11 --no-cpu-baseline --no-modes --no-host-measure 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); print('step', round(d['ms_per_step'],3), round(d['roofline']['frac'],4))"
 done

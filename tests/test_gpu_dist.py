@@ -108,12 +108,12 @@ def test_rccl_single_rank_sync_batchnorm(tmp_path):
 @pytest.mark.parametrize('world', [2, 8])
 def test_bench_launches_its_own_ranks(world):
     """`python bench.py --gpus N` (N = 2, and N = 8 with the `other_workloads` block: the command of
-    the driver's scaling run) as the driver may call it (no WORLD_SIZE in the environment): the
-    script re-executes itself under torch.distributed.run, both ranks initialise a process group,
-    shard the batch, all-reduce their gradients from inside the backward passes and rank 0 prints
+    the driver's scaling run; --full for the `comm` block) as the driver may call it (no WORLD_SIZE
+    in the environment): the script runs itself as a child under torch.distributed.run, both ranks
+    initialise a process group, shard the batch, all-reduce their gradients from inside the backward passes and rank 0 prints
     ONE JSON line for the whole job.  A one-GPU box cannot host two RCCL ranks, so the two ranks
     share cuda:0 over gloo (SEGAN_DIST_BACKEND / SEGAN_LOCAL_DEVICE test hooks); everything else —
-    the exec, the rendezvous on 127.0.0.1, the rank bookkeeping, the barriers and the max-over-ranks
+    the child launch, the rendezvous on 127.0.0.1, the rank bookkeeping, the barriers and the max-over-ranks
     timing — is the code the 8-GPU run executes."""
     import json
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -122,7 +122,7 @@ def test_bench_launches_its_own_ranks(world):
         env.pop(k, None)
     batch = 12 if world == 2 else 8
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(world), '--steps', '2',
-                        '--warmup', '1', '--batch', str(batch), '--no-cpu-baseline', '--no-modes'] +
+                        '--warmup', '1', '--batch', str(batch), '--full', '--no-cpu-baseline', '--no-modes'] +
                        (['--no-side-workloads'] if world == 2 else ['--side-steps', '1']),
                        capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
