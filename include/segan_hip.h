@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SEGAN_ABI_VERSION 13
+#define SEGAN_ABI_VERSION 14
 
 #define SEGAN_PAD_REFLECT 0
 #define SEGAN_PAD_ZERO 1
@@ -394,6 +394,16 @@ int segan_deemphasis(const float* y, float* x, int rows, int T, double coef, voi
 int segan_ssnr_frames(int T, int srate);
 int segan_ssnr(const float* ref, const float* deg, float* seg, float* out, int rows, int T,
                int srate, double eps, void* stream);
+/* Per-frame objective quality measures of the reference's CompositeEval, fp64 like numpy, on the
+ * SSNR frames (nframes = segan_ssnr_frames(T, srate); nothing is launched when it is 0) of
+ * ref / deg [rows][T]; dist[rows][nframes].  srate: a 30 ms window of 4 .. 1024 samples.
+ *   segan_wss: weighted spectral slope distortion (utils.py:442-596);
+ *   segan_llr: log-likelihood ratio (utils.py:598-716), LPC order 16 (srate >= 10000) or 10;
+ *              NaN where the clean frame is digital silence. */
+int segan_wss(const float* ref, const float* deg, double* dist, int rows, int T, int srate,
+              void* stream);
+int segan_llr(const float* ref, const float* deg, double* dist, int rows, int T, int srate,
+              void* stream);
 
 /* ---- optimizers (model.py:219-228) ---------------------------------------------------- */
 /* torch.optim.RMSprop (no momentum, not centered): sq = alpha*sq + (1-alpha)*g*g;

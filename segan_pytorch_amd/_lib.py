@@ -14,7 +14,7 @@ PAD_REFLECT = 0
 PAD_ZERO = 1
 ACT_NONE = 0
 ACT_TANH = 1
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 
 class SeganSrc(Structure):
@@ -94,6 +94,8 @@ SIGNATURES = {
     'segan_deemphasis': (c_int, [_P, _P, c_int, c_int, c_double, _P]),
     'segan_ssnr_frames': (c_int, [c_int, c_int]),
     'segan_ssnr': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_double, _P]),
+    'segan_wss': (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
+    'segan_llr': (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     'segan_rmsprop_step': (c_int, [_P, _P, _P, c_float, c_float, c_float, c_int64, _P]),
     'segan_adam_step': (c_int, [_P, _P, _P, _P, c_float, c_float, c_float, c_float, c_int, c_int64,
                                 _P]),

@@ -1,0 +1,363 @@
+// segan_quality.hip — per-frame objective speech-quality measures of the reference's evaluation
+// (segan/utils.py): weighted spectral slope (WSS, utils.py:442-596) and log-likelihood ratio
+// (LLR, utils.py:598-716).  Both use the SSNR frame geometry (win = round(30 ms), hop win/4,
+// segan_ssnr_frames) and the Hann-like window 0.5*(1 - cos(2*pi*k/(win+1))), k = 1..win, and
+// compute in fp64 like numpy.  The window, the DFT twiddles and the critical-band table are built
+// on the host with the reference's own expressions and uploaded once per (device, srate).
+#include "segan_common.h"
+#include <math.h>
+#include <deque>
+#include <mutex>
+#include <vector>
+
+#define QW_NCRIT 25
+#define QW_THREADS 256
+
+namespace {
+
+struct QualityTables {
+  int device, srate, win, skip, nfft, klo, nb;
+  double* window;   // [win]
+  double2* tw;      // [nfft]: (cos, sin)(2*pi*m/nfft)
+  double* crit;     // [QW_NCRIT][nb]: utils.py:472-497 restricted to bins klo .. klo+nb-1
+};
+
+std::mutex g_tables_mu;
+std::deque<QualityTables> g_tables;   // push_back keeps earlier elements in place
+
+// utils.py:448-451 / 600-605: window length and hop (the SSNR ones: segan_ssnr_frames)
+void frame_geometry(int srate, int* win, int* skip) {
+  *win = (int)__builtin_round(30.0 * srate / 1000.0);
+  *skip = *win / 4;
+}
+
+int nfft_of(int win) {   // utils.py:455: int(2 ** np.ceil(np.log(2*winlength)/np.log(2)))
+  return (int)pow(2.0, ceil(log(2.0 * win) / log(2.0)));
+}
+
+// Returns the tables of (current device, srate), building and uploading them on first use.
+const QualityTables* get_tables(int srate) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) {
+    segan_set_error("quality: hipGetDevice failed");
+    return nullptr;
+  }
+  std::lock_guard<std::mutex> lock(g_tables_mu);
+  for (const QualityTables& t : g_tables)
+    if (t.device == dev && t.srate == srate) return &t;
+
+  QualityTables t{};
+  t.device = dev;
+  t.srate = srate;
+  frame_geometry(srate, &t.win, &t.skip);
+  t.nfft = nfft_of(t.win);
+  const int half = t.nfft / 2;
+  // utils.py:537-538: time = np.linspace(1, win, win) / (win + 1); 0.5 * (1 - cos(2*pi*time))
+  std::vector<double> window(t.win);
+  for (int k = 0; k < t.win; ++k) {
+    const double time = (double)(k + 1) / (double)(t.win + 1);
+    window[k] = 0.5 * (1.0 - cos(2.0 * M_PI * time));
+  }
+  std::vector<double2> tw(t.nfft);
+  for (int m = 0; m < t.nfft; ++m) {
+    const double ang = 2.0 * M_PI * (double)m / (double)t.nfft;
+    tw[m] = make_double2(cos(ang), sin(ang));
+  }
+  // utils.py:463-497: Gaussian critical-band filters, zeroed below the -30 dB point
+  static const double cent_freq[QW_NCRIT] = {
+      50., 120, 190, 260, 330, 400, 470, 540, 617.372, 703.378, 798.717, 904.128, 1020.38,
+      1148.30, 1288.72, 1442.54, 1610.70, 1794.16, 1993.93, 2211.08, 2446.71, 2701.97, 2978.04,
+      3276.17, 3597.63};
+  static const double bandwidth[QW_NCRIT] = {
+      70., 70, 70, 70, 70, 70, 70, 77.3724, 86.0056, 95.3398, 105.411, 116.256, 127.914,
+      140.423, 153.823, 168.154, 183.457, 199.776, 217.153, 235.631, 255.255, 276.072, 298.126,
+      321.465, 346.136};
+  const double max_freq = srate / 2.0;
+  const double bw_min = bandwidth[0];
+  const double min_factor = exp(-30. / (2 * 2.303));
+  std::vector<double> full((size_t)QW_NCRIT * half);
+  int lo = half, hi = 0;
+  for (int i = 0; i < QW_NCRIT; ++i) {
+    const double f0 = floor((cent_freq[i] / max_freq) * half);
+    const double bw = (bandwidth[i] / max_freq) * half;
+    const double norm_factor = log(bw_min) - log(bandwidth[i]);
+    for (int j = 0; j < half; ++j) {
+      const double u = (j - f0) / bw;
+      const double v = exp(-11 * (u * u) + norm_factor);
+      const double w = v > min_factor ? v : 0.0;
+      full[(size_t)i * half + j] = w;
+      if (w != 0.0) {
+        lo = j < lo ? j : lo;
+        hi = j + 1 > hi ? j + 1 : hi;
+      }
+    }
+  }
+  if (hi <= lo) {
+    segan_set_error("quality: no critical band has a non-zero weight at srate %d", srate);
+    return nullptr;
+  }
+  t.klo = lo;
+  t.nb = hi - lo;
+  std::vector<double> crit((size_t)QW_NCRIT * t.nb);
+  for (int i = 0; i < QW_NCRIT; ++i)
+    for (int b = 0; b < t.nb; ++b) crit[(size_t)i * t.nb + b] = full[(size_t)i * half + lo + b];
+
+  if (hipMalloc(&t.window, window.size() * sizeof(double)) != hipSuccess ||
+      hipMalloc(&t.tw, tw.size() * sizeof(double2)) != hipSuccess ||
+      hipMalloc(&t.crit, crit.size() * sizeof(double)) != hipSuccess ||
+      hipMemcpy(t.window, window.data(), window.size() * sizeof(double), hipMemcpyHostToDevice) !=
+          hipSuccess ||
+      hipMemcpy(t.tw, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(t.crit, crit.data(), crit.size() * sizeof(double), hipMemcpyHostToDevice) !=
+          hipSuccess) {
+    segan_set_error("quality: table upload failed");
+    return nullptr;
+  }
+  g_tables.push_back(t);
+  return &g_tables.back();
+}
+
+}  // namespace
+
+__device__ __forceinline__ double wave_sum_all(double v) {   // result in every lane
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// the windowed (clean, processed) frame f of row blockIdx.y as fp64 pairs: fr[k] = (c, p)
+__device__ __forceinline__ void load_frame_pair(double2* fr, const float* __restrict__ ref,
+                                                const float* __restrict__ deg,
+                                                const double* __restrict__ window, int T,
+                                                int f, int win, int skip, int t, int nt) {
+  const size_t base = (size_t)blockIdx.y * T + (size_t)f * skip;
+  for (int k = t; k < win; k += nt) {
+    const double w = window[k];
+    fr[k] = make_double2((double)ref[base + k] * w, (double)deg[base + k] * w);
+  }
+}
+
+// ---------------------------------------------------------------------------------
+// WSS.  One 256-thread workgroup per (frame, row).  LDS: the windowed pair, the twiddles, the
+// power of both spectra over the bins [klo, klo+nb) that some band weighs (a direct fp64 DFT:
+// |sum_n x[n] e^{-2 pi i k n / nfft}|^2, the zero padding of np.fft.fft(x, nfft) contributes
+// nothing).  Then 50 band energies (one wave each, lanes over bins), and one lane per band for
+// dB, slope, nearest peak and weight, summed across the wave.
+// ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(QW_THREADS) void wss_kernel(
+    const float* __restrict__ ref, const float* __restrict__ deg, double* __restrict__ dist, int T,
+    int nframes, int win, int skip, int nfft, int klo, int nb, const double* __restrict__ window,
+    const double2* __restrict__ twg, const double* __restrict__ crit) {
+  extern __shared__ double2 qsh[];
+  double2* fr = qsh;              // [win]
+  double2* tw = fr + win;         // [nfft]
+  double2* spec = tw + nfft;      // [nb]: (clean, processed) power
+  __shared__ double energy[2][QW_NCRIT];   // dB
+  __shared__ double slope[2][QW_NCRIT];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int f = blockIdx.x;
+  load_frame_pair(fr, ref, deg, window, T, f, win, skip, t, QW_THREADS);
+  for (int m = t; m < nfft; m += QW_THREADS) tw[m] = twg[m];
+  __syncthreads();
+
+  const int mask = nfft - 1;   // nfft is a power of two
+  for (int b = t; b < nb; b += QW_THREADS) {
+    const int k = klo + b;
+    double cr = 0.0, ci = 0.0, pr = 0.0, pi = 0.0;
+    int idx = 0;
+    for (int n = 0; n < win; ++n) {
+      const double2 x = fr[n];
+      const double2 w = tw[idx];
+      cr = fma(x.x, w.x, cr);
+      ci = fma(x.x, w.y, ci);
+      pr = fma(x.y, w.x, pr);
+      pi = fma(x.y, w.y, pi);
+      idx = (idx + k) & mask;
+    }
+    spec[b] = make_double2(cr * cr + ci * ci, pr * pr + pi * pi);
+  }
+  __syncthreads();
+
+  // band energies: (band, signal) pairs over the four waves
+  for (int j = wave; j < 2 * QW_NCRIT; j += QW_THREADS / 64) {
+    const int band = j % QW_NCRIT, sig = j / QW_NCRIT;
+    const double* cw = crit + (size_t)band * nb;
+    double e = 0.0;
+    for (int b = lane; b < nb; b += 64) e = fma(sig ? spec[b].y : spec[b].x, cw[b], e);
+    e = wave_sum_all(e);
+    // 10*log10(max(E, 1e-10)), NaN propagating like np.max
+    if (lane == 0) energy[sig][band] = 10.0 * log10(e < 1e-10 ? 1e-10 : e);
+  }
+  __syncthreads();
+  if (wave == 0 && lane < QW_NCRIT - 1) {
+    slope[0][lane] = energy[0][lane + 1] - energy[0][lane];
+    slope[1][lane] = energy[1][lane + 1] - energy[1][lane];
+  }
+  __syncthreads();
+  if (wave != 0) return;
+  const double Kmax = 20.0, Klocmax = 1.0;
+  double num = 0.0, den = 0.0;
+  if (lane < QW_NCRIT - 1) {
+    const int i = lane;
+    double W = 0.0;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const double* e = energy[s];
+      const double* sl = slope[s];
+      // utils.py:541-560, off-by-one of the right search included
+      double peak;
+      int n = i;
+      if (sl[i] > 0) {
+        while (n < QW_NCRIT - 1 && sl[n] > 0) ++n;
+        peak = e[n - 1];
+      } else {
+        while (n >= 0 && sl[n] <= 0) --n;
+        peak = e[n + 1];
+      }
+      double dBmax = e[0];   // python max(): first of the largest
+      for (int m = 1; m < QW_NCRIT; ++m)
+        if (e[m] > dBmax) dBmax = e[m];
+      const double wmax = Kmax / (Kmax + dBmax - e[i]);
+      const double wloc = Klocmax / (Klocmax + peak - e[i]);
+      W += wmax * wloc;
+    }
+    W = W / 2;
+    const double d = slope[0][i] - slope[1][i];
+    num = W * (d * d);
+    den = W;
+  }
+  num = wave_sum_all(num);
+  den = wave_sum_all(den);
+  if (lane == 0) dist[(size_t)blockIdx.y * nframes + f] = num / den;
+}
+
+// ---------------------------------------------------------------------------------
+// LLR.  One wave per (frame, row), four frames per workgroup.  Lags 0..P of both windowed
+// frames (lanes over samples, butterfly sums), Levinson-Durbin in fp64 (lpcoeff, utils.py:
+// 659-716) in every lane, R and [1, -a] rounded to fp32 as lpcoeff returns them, both quadratic
+// forms A toeplitz(R_clean) A^T in fp64 from those, log of the ratio.  R_clean[0] == 0 yields NaN.
+// ---------------------------------------------------------------------------------
+template <int P>
+__device__ __forceinline__ void levinson_lpc(const double (&R)[P + 1], double (&A)[P + 1]) {
+  double a[P];
+#pragma unroll
+  for (int j = 0; j < P; ++j) a[j] = 1.0;
+  double E = R[0];
+#pragma unroll
+  for (int i = 0; i < P; ++i) {
+    double sum = 0.0;
+#pragma unroll
+    for (int j = 0; j < i; ++j) sum += a[j] * R[i - j];
+    const double rc = (R[i + 1] - sum) / E;
+    double na[P];
+#pragma unroll
+    for (int j = 0; j < i; ++j) na[j] = a[j] - rc * a[i - 1 - j];
+#pragma unroll
+    for (int j = 0; j < i; ++j) a[j] = na[j];
+    a[i] = rc;
+    E = (1 - rc * rc) * E;
+  }
+  A[0] = 1.0;
+#pragma unroll
+  for (int j = 0; j < P; ++j) A[j + 1] = (double)(float)(-a[j]);
+}
+
+template <int P>
+__device__ __forceinline__ double quad_toeplitz(const double (&A)[P + 1], const double (&R)[P + 1]) {
+  double q = 0.0;
+#pragma unroll
+  for (int i = 0; i <= P; ++i) {
+    double r = 0.0;
+#pragma unroll
+    for (int j = 0; j <= P; ++j) r += A[j] * R[i > j ? i - j : j - i];
+    q += A[i] * r;
+  }
+  return q;
+}
+
+template <int P>
+__global__ __launch_bounds__(QW_THREADS) void llr_kernel(
+    const float* __restrict__ ref, const float* __restrict__ deg, double* __restrict__ dist, int T,
+    int nframes, int win, int skip, const double* __restrict__ window) {
+  extern __shared__ double2 qsh[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int f = blockIdx.x * (QW_THREADS / 64) + wave;
+  double2* fr = qsh + (size_t)wave * win;
+  if (f < nframes) load_frame_pair(fr, ref, deg, window, T, f, win, skip, lane, 64);
+  __syncthreads();
+  if (f >= nframes) return;   // whole waves leave; no barrier below
+
+  double Rc[P + 1], Rp[P + 1];
+#pragma unroll
+  for (int j = 0; j <= P; ++j) Rc[j] = Rp[j] = 0.0;
+  for (int n = lane; n < win; n += 64) {
+    const double2 x = fr[n];
+#pragma unroll
+    for (int j = 0; j <= P; ++j) {
+      if (n + j < win) {
+        const double2 y = fr[n + j];
+        Rc[j] = fma(x.x, y.x, Rc[j]);
+        Rp[j] = fma(x.y, y.y, Rp[j]);
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j <= P; ++j) {
+    Rc[j] = wave_sum_all(Rc[j]);
+    Rp[j] = wave_sum_all(Rp[j]);
+  }
+  double Ac[P + 1], Ap[P + 1];
+  levinson_lpc<P>(Rc, Ac);
+  levinson_lpc<P>(Rp, Ap);
+  double Rcf[P + 1];
+#pragma unroll
+  for (int j = 0; j <= P; ++j) Rcf[j] = (double)(float)Rc[j];
+  const double numer = quad_toeplitz<P>(Ap, Rcf);
+  const double denom = quad_toeplitz<P>(Ac, Rcf);
+  if (lane == 0) dist[(size_t)blockIdx.y * nframes + f] = log(numer / denom);
+}
+
+static int quality_args(const char* what, const float* ref, const float* deg, const double* dist,
+                        int rows, int T, int srate) {
+  SEGAN_REQUIRE(ref && deg && dist, "%s: NULL pointer", what);
+  SEGAN_REQUIRE(rows > 0 && rows <= 65535 && T > 0, "%s: bad sizes rows=%d T=%d", what, rows, T);
+  int win, skip;
+  frame_geometry(srate > 0 ? srate : 0, &win, &skip);
+  // 2*win <= 2048 keeps the frames and twiddles of either kernel within 64 KiB of LDS
+  SEGAN_REQUIRE(srate > 0 && skip > 0 && nfft_of(win) <= 2048,
+                "%s: srate %d unsupported (30 ms window of 4 .. 1024 samples)", what, srate);
+  return SEGAN_OK;
+}
+
+extern "C" int segan_wss(const float* ref, const float* deg, double* dist, int rows, int T,
+                         int srate, void* stream) {
+  if (int e = quality_args("wss", ref, deg, dist, rows, T, srate)) return e;
+  const int nf = segan_ssnr_frames(T, srate);
+  if (nf == 0) return SEGAN_OK;
+  const QualityTables* tb = get_tables(srate);
+  if (!tb) return SEGAN_ELAUNCH;
+  const size_t lds = (size_t)(tb->win + tb->nfft + tb->nb) * sizeof(double2);
+  hipLaunchKernelGGL(wss_kernel, dim3(nf, rows), dim3(QW_THREADS), lds, (hipStream_t)stream, ref,
+                     deg, dist, T, nf, tb->win, tb->skip, tb->nfft, tb->klo, tb->nb, tb->window,
+                     tb->tw, tb->crit);
+  return segan_check_launch("wss_kernel");
+}
+
+extern "C" int segan_llr(const float* ref, const float* deg, double* dist, int rows, int T,
+                         int srate, void* stream) {
+  if (int e = quality_args("llr", ref, deg, dist, rows, T, srate)) return e;
+  const int nf = segan_ssnr_frames(T, srate);
+  if (nf == 0) return SEGAN_OK;
+  const QualityTables* tb = get_tables(srate);
+  if (!tb) return SEGAN_ELAUNCH;
+  const size_t lds = (size_t)(QW_THREADS / 64) * tb->win * sizeof(double2);
+  const dim3 grid(ceil_div(nf, QW_THREADS / 64), rows);
+  hipStream_t st = (hipStream_t)stream;
+  if (srate >= 10000)   // utils.py:607-611: LPC order
+    hipLaunchKernelGGL(llr_kernel<16>, grid, dim3(QW_THREADS), lds, st, ref, deg, dist, T, nf,
+                       tb->win, tb->skip, tb->window);
+  else
+    hipLaunchKernelGGL(llr_kernel<10>, grid, dim3(QW_THREADS), lds, st, ref, deg, dist, T, nf,
+                       tb->win, tb->skip, tb->window);
+  return segan_check_launch("llr_kernel");
+}

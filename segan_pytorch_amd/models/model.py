@@ -415,17 +415,20 @@ class SEGAN(Model):
 
     def evaluate(self, opts, dloader, log_freq, do_noisy=False, max_samples=1, device='cpu'):
         """Objective evaluation on a validation loader (model.py:440-507), on the GPU: G in eval
-        mode on up to `max_samples` batches, de-emphasis, segmental SNR (utils.py:350-395) of the
-        enhanced — and with `do_noisy` of the noisy — signal against the clean one.  Returns
-        {'ssnr': [...], 'snr': [...]} per utterance (and the same for the noisy input).  PESQ /
-        CSIG / CBAK / COVL of the reference need its external `pesqmain` binary and are not
-        computed.  De-emphasis runs along time (the reference applies it along axis 0 of the
-        [B, T] batch, model.py:474-477)."""
-        from .. import ops
+        mode on up to `max_samples` batches, de-emphasis, then per utterance the segmental and
+        overall SNR (utils.py:350-395: keys 'ssnr', 'snr') and the reference's composite measures
+        (quality.composite_eval, utils.py:397-440: 'pesq', 'csig', 'cbak', 'covl', 'wss', 'llr')
+        of the enhanced — and with `do_noisy` of the noisy — signal against the clean one.  PESQ
+        comes from the external `pesqmain` binary (run in `opts.eval_workers` threads, at most
+        16); without it on PATH pesq / csig / cbak / covl are NaN.  De-emphasis runs along time
+        (the reference applies it along axis 0 of the [B, T] batch, model.py:474-477)."""
+        from .. import ops, quality
         self.G.eval()
         self.D.eval()
-        evals = {'ssnr': [], 'snr': []}
-        noisy_evals = {'ssnr': [], 'snr': []}
+        keys = ('ssnr', 'snr', 'pesq', 'csig', 'cbak', 'covl', 'wss', 'llr')
+        evals = {k: [] for k in keys}
+        noisy_evals = {k: [] for k in keys}
+        workers = getattr(opts, 'eval_workers', 2)
         with torch.no_grad():
             for bidx, batch in enumerate(dloader, start=1):
                 if len(batch) != 4:
@@ -436,9 +439,13 @@ class SEGAN(Model):
                 Genh = self.infer_G(noisy.unsqueeze(1)).squeeze(1).contiguous()
                 c = ops.de_emphasize(clean, self.preemph)
                 for sig, dst in ((Genh, evals),) + (((noisy, noisy_evals),) if do_noisy else ()):
-                    snr, ssnr, _ = ops.ssnr(c, ops.de_emphasize(sig, self.preemph))
+                    d = ops.de_emphasize(sig, self.preemph)
+                    snr, ssnr, _ = ops.ssnr(c, d)
                     dst['ssnr'] += ssnr.cpu().tolist()
                     dst['snr'] += snr.cpu().tolist()
+                    comp = quality.composite_eval(c, d, workers=workers)
+                    for k in ('pesq', 'csig', 'cbak', 'covl', 'wss', 'llr'):
+                        dst[k] += comp[k].cpu().tolist()
                 if bidx >= max_samples:
                     break
         self.G.train()

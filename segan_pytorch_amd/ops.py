@@ -1038,6 +1038,30 @@ def ssnr(ref, deg, srate=16000, eps=1e-10):
     return out[:, 0], out[:, 1], seg[:, :nf]
 
 
+def _quality_frames(fn, what, ref, deg, srate):
+    _chk(ref, 'ref', 2)
+    _chk(deg, 'deg', 2)
+    if ref.shape != deg.shape:
+        raise ValueError('{}: shapes differ {} vs {}'.format(what, tuple(ref.shape), tuple(deg.shape)))
+    rows, T = ref.shape
+    nf = _lib.load().segan_ssnr_frames(T, srate)
+    dist = torch.empty((rows, max(nf, 1)), device=ref.device, dtype=torch.float64)
+    check(fn(_ptr(ref), _ptr(deg), _ptr(dist), rows, T, srate, _stream()), what)
+    return dist[:, :nf]
+
+
+def wss(ref, deg, srate=16000):
+    """Per-frame weighted spectral slope distortion of utils.py:442-596 for the rows of ref / deg
+    [rows, T] on the device: fp64 [rows, nframes] (the SSNR frames)."""
+    return _quality_frames(_lib.load().segan_wss, 'wss', ref, deg, srate)
+
+
+def llr(ref, deg, srate=16000):
+    """Per-frame log-likelihood ratio of utils.py:598-716 for the rows of ref / deg [rows, T] on
+    the device: fp64 [rows, nframes]; NaN where the clean frame is all zeros."""
+    return _quality_frames(_lib.load().segan_llr, 'llr', ref, deg, srate)
+
+
 def rmsprop_step(p, g, sq, lr, alpha, eps):
     check(_lib.load().segan_rmsprop_step(_ptr(p), _ptr(g), _ptr(sq), lr, alpha, eps, p.numel(),
                                          _stream()), 'rmsprop_step')

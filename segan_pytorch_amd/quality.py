@@ -1,0 +1,173 @@
+"""Objective speech-quality evaluation of the reference's segan/utils.py:299-440 on the device:
+CSIG / CBAK / COVL (Hu & Loizou's composite measures) from WSS, LLR, segmental SNR and PESQ.
+
+The per-frame measures are HIP kernels (``ops.wss``, ``ops.llr``, ``ops.ssnr``); the trimmed means
+and the three linear formulas are a few hundred numbers per row and run as torch ops on the device.
+PESQ is the external ITU-T P.862 ``pesqmain`` binary, called like the reference does.
+"""
+import math
+import os
+import re
+import shutil
+import subprocess
+import tempfile
+import threading
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+from . import ops
+
+ALPHA = 0.95
+SRATE = 16000
+MAX_WORKERS = 16
+PESQ_NOT_FOUND = 'pesqmain not found! Please add it your PATH'
+
+_warned = False
+_warn_lock = threading.Lock()
+
+
+def trimmed_count(n, alpha=ALPHA):
+    """How many of the n ascending frame values the alpha-trimmed mean keeps: Python's round
+    (half to even) of the float product, as utils.py:410-417 (n = 30 keeps 28)."""
+    return int(round(n * alpha))
+
+
+def _pesq_missing():
+    global _warned
+    with _warn_lock:
+        if not _warned:
+            _warned = True
+            print(PESQ_NOT_FOUND)
+
+
+def pesq_raw(ref, deg, srate=SRATE):
+    """The last token of ``pesqmain ref.wav deg.wav +16000 +wb``'s second-last output line (the
+    string utils.py:318-347 returns), or None when pesqmain is not on PATH (the message is
+    printed once per process).  Both signals go through 16-bit PCM wav files (x * 32767, rounded to
+    nearest, clipped), which are deleted afterwards."""
+    from scipy.io import wavfile
+    exe = shutil.which('pesqmain')
+    if exe is None:
+        _pesq_missing()
+        return None
+    paths = []
+    try:
+        for tag, x in (('ref', ref), ('deg', deg)):
+            fd, path = tempfile.mkstemp(suffix='_{}.wav'.format(tag))
+            os.close(fd)
+            paths.append(path)
+            x = np.asarray(x, dtype=np.float64).reshape(-1)
+            pcm = np.clip(np.rint(x * 32767), -32768, 32767).astype(np.int16)
+            wavfile.write(path, srate, pcm)
+        p = subprocess.run([exe, paths[0], paths[1], '+{}'.format(srate), '+wb'],
+                           stdout=subprocess.PIPE, encoding='ascii', errors='replace')
+        if 'error!' in p.stdout:
+            return 'error!'
+        lines = p.stdout.split('\n')
+        if len(lines) < 2:
+            raise RuntimeError('pesqmain: unexpected output {!r}'.format(p.stdout))
+        return re.split(r'\s+', lines[-2])[-1]
+    finally:
+        for path in paths:
+            try:
+                os.remove(path)
+            except OSError:
+                pass
+
+
+def _pesq_value(raw):
+    """utils.py:421-424: a string containing 'error!' is -1, otherwise its float; None (no
+    pesqmain) is NaN."""
+    if raw is None:
+        return math.nan
+    if isinstance(raw, str):
+        return -1.0 if 'error!' in raw else float(raw)
+    return float(raw)
+
+
+def pesq_score(ref_np, deg_np):
+    """PESQ (wide band, 16 kHz) of two numpy signals through pesqmain: float, -1 on a pesqmain
+    error, NaN without pesqmain."""
+    return _pesq_value(pesq_raw(ref_np, deg_np))
+
+
+def _trimmed_mean(frames, k):
+    return torch.sort(frames, dim=1).values[:, :k].mean(dim=1)
+
+
+def _as_rows(x, name):
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RuntimeError('{} must be a CUDA (HIP) tensor: segan_pytorch_amd runs only on an '
+                           'MI355X (HIP) device; there is no CPU path'.format(name))
+    if x.dim() == 1:
+        x = x.unsqueeze(0)
+    if x.dim() != 2:
+        raise ValueError('{} must be [rows, T] or [T], got {}'.format(name, tuple(x.shape)))
+    return x
+
+
+def composite_eval(ref, deg, pesq=None, workers=2):
+    """CompositeEval (utils.py:397-440) of each row of ref / deg ([rows, T] or [T] CUDA tensors,
+    16 kHz), truncated to the common length.  Returns a dict of fp64 device tensors [rows]:
+    csig, cbak, covl, pesq, ssnr (mean segmental SNR), wss, llr (0.95-trimmed means).
+
+    pesq: None runs pesqmain on each row (in a pool of ``min(workers, 16)`` threads); otherwise
+    one value or one per row, each a number or a pesqmain result string ('error!' -> -1).
+
+    Edge cases:
+      * a row with any non-finite frame LLR (a clean frame of digital silence) has llr = NaN, and
+        so csig and covl are NaN; cbak stays finite.  (The reference's result there depends on
+        where Python's sort leaves the NaN.)
+      * fewer samples than one frame (T < win + hop, 600 at 16 kHz): every measure is NaN, pesq
+        included (pesqmain is not called).
+      * without pesqmain on PATH (and pesq=None): pesq, csig, cbak and covl are NaN; wss, llr and
+        ssnr are still computed.
+    """
+    ref = _as_rows(ref, 'ref')
+    deg = _as_rows(deg, 'deg')
+    if ref.shape[0] != deg.shape[0]:
+        raise ValueError('ref and deg have {} and {} rows'.format(ref.shape[0], deg.shape[0]))
+    L = min(ref.shape[1], deg.shape[1])
+    ref = ref[:, :L].float().contiguous()
+    deg = deg[:, :L].float().contiguous()
+    rows, dev = ref.shape[0], ref.device
+    f64 = dict(device=dev, dtype=torch.float64)
+
+    wss_f = ops.wss(ref, deg, SRATE)
+    llr_f = ops.llr(ref, deg, SRATE)
+    _, _, seg = ops.ssnr(ref, deg, SRATE)
+    nf = wss_f.shape[1]
+    if nf == 0:
+        nan = torch.full((rows,), math.nan, **f64)
+        return {k: nan.clone() for k in ('csig', 'cbak', 'covl', 'pesq', 'ssnr', 'wss', 'llr')}
+    k = trimmed_count(nf)
+    wss_m = _trimmed_mean(wss_f, k)
+    llr_m = _trimmed_mean(llr_f, k)
+    llr_m = torch.where(torch.isfinite(llr_f).all(dim=1), llr_m, torch.full_like(llr_m, math.nan))
+    ssnr_m = seg.double().mean(dim=1)
+
+    if pesq is None:
+        r_np, d_np = ref.cpu().numpy(), deg.cpu().numpy()
+        if shutil.which('pesqmain') is None:
+            _pesq_missing()
+            vals = [math.nan] * rows
+        elif rows == 1:
+            vals = [pesq_score(r_np[0], d_np[0])]
+        else:
+            with ThreadPoolExecutor(max_workers=max(1, min(int(workers), MAX_WORKERS))) as pool:
+                vals = list(pool.map(pesq_score, r_np, d_np))
+    elif isinstance(pesq, (str, bytes, int, float)):
+        vals = [_pesq_value(pesq)] * rows
+    else:
+        vals = [_pesq_value(v) for v in pesq]
+        if len(vals) != rows:
+            raise ValueError('pesq has {} values for {} rows'.format(len(vals), rows))
+    pesq_t = torch.tensor(vals, **f64)
+
+    csig = (3.093 - 1.029 * llr_m + 0.603 * pesq_t - 0.009 * wss_m).clamp(1, 5)
+    cbak = (1.634 + 0.478 * pesq_t - 0.007 * wss_m + 0.063 * ssnr_m).clamp(1, 5)
+    covl = (1.594 + 0.805 * pesq_t - 0.512 * llr_m - 0.007 * wss_m).clamp(1, 5)
+    return {'csig': csig, 'cbak': cbak, 'covl': covl, 'pesq': pesq_t, 'ssnr': ssnr_m,
+            'wss': wss_m, 'llr': llr_m}
