@@ -1,10 +1,12 @@
 """Composite evaluation (CSIG / CBAK / COVL / PESQ / SSNR) of a directory of degraded wavs against
 the clean wavs of the same names, on the MI355X: the reference's eval_noisy_performance.py.
 
-    python eval_noisy_performance.py --test_wavs DIR --clean_wavs DIR --logfile FILE
+    python eval_noisy_performance.py --test_wavs DIR --clean_wavs DIR --logfile FILE [--stoi]
 
 16 kHz wavs only (int16 files are scaled by 1/32768, float files used as they are); PESQ needs
-the external `pesqmain` on PATH (NaN, and so NaN CSIG / CBAK / COVL, without it)."""
+the external `pesqmain` on PATH (NaN, and so NaN CSIG / CBAK / COVL, without it).  --stoi adds
+a STOI column (quality.stoi on the GPU, both files truncated to their common length) and a final
+mean STOI line."""
 import argparse
 import glob
 import os
@@ -40,12 +42,12 @@ def main(opts):
     if not torch.cuda.is_available():
         raise SystemExit('segan_pytorch_amd runs only on an MI355X (HIP) device; pass --cuda on a '
                          'GPU machine (there is no CPU fallback)')
-    from segan_pytorch_amd.quality import composite_eval
+    from segan_pytorch_amd.quality import composite_eval, stoi
     noisy_wavs = sorted(glob.glob(os.path.join(opts.test_wavs, '*.wav')))
-    metrics = {'csig': [], 'cbak': [], 'covl': []}
+    metrics = {'csig': [], 'cbak': [], 'covl': [], 'stoi': []}
     timings = []
     with open(opts.logfile, 'w') as out_log:
-        out_log.write('FILE CSIG CBAK COVL PESQ SSNR\n')
+        out_log.write('FILE CSIG CBAK COVL PESQ SSNR' + (' STOI' if opts.stoi else '') + '\n')
         for n_i, noisy_wav in enumerate(noisy_wavs, start=1):
             bname = os.path.splitext(os.path.basename(noisy_wav))[0]
             clean_wav = os.path.join(opts.clean_wavs, bname + '.wav')
@@ -55,13 +57,18 @@ def main(opts):
             r = composite_eval(torch.from_numpy(clean).cuda(), torch.from_numpy(noisy).cuda())
             csig, cbak, covl, pesq, ssnr = (float(r[k][0]) for k in
                                             ('csig', 'cbak', 'covl', 'pesq', 'ssnr'))
+            if opts.stoi:
+                L = min(len(clean), len(noisy))
+                metrics['stoi'].append(float(stoi(torch.from_numpy(clean[:L]).cuda(),
+                                                  torch.from_numpy(noisy[:L]).cuda())[0]))
             end_t = timeit.default_timer()
             timings.append(end_t - beg_t)
             metrics['csig'].append(csig)
             metrics['cbak'].append(cbak)
             metrics['covl'].append(covl)
-            out_log.write('{} {:.3f} {:.3f} {:.3f} {:.3f} {:.3}\n'.format(bname + '.wav', csig,
-                                                                          cbak, covl, pesq, ssnr))
+            out_log.write('{} {:.3f} {:.3f} {:.3f} {:.3f} {:.3}'.format(bname + '.wav', csig,
+                                                                        cbak, covl, pesq, ssnr) +
+                          (' {:.4f}'.format(metrics['stoi'][-1]) if opts.stoi else '') + '\n')
             print('Processed {}/{} wav, CSIG:{:.3f} CBAK:{:.3f} COVL:{:.3f} '
                   'PESQ:{:.3f} SSNR:{:.3f} '
                   'total time: {:.2f} seconds, mproc: {:.2f}'
@@ -70,6 +77,8 @@ def main(opts):
     print('mean Csig: ', np.mean(metrics['csig']))
     print('mean Cbak: ', np.mean(metrics['cbak']))
     print('mean Covl: ', np.mean(metrics['covl']))
+    if opts.stoi:
+        print('mean STOI: ', np.mean(metrics['stoi']))
 
 
 if __name__ == '__main__':
@@ -77,4 +86,6 @@ if __name__ == '__main__':
     parser.add_argument('--test_wavs', type=str, required=True)
     parser.add_argument('--clean_wavs', type=str, required=True)
     parser.add_argument('--logfile', type=str, required=True)
+    parser.add_argument('--stoi', action='store_true', default=False,
+                        help='also compute STOI (short-time objective intelligibility)')
     main(parser.parse_args())

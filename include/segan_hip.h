@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SEGAN_ABI_VERSION 14
+#define SEGAN_ABI_VERSION 15
 
 #define SEGAN_PAD_REFLECT 0
 #define SEGAN_PAD_ZERO 1
@@ -404,6 +404,29 @@ int segan_wss(const float* ref, const float* deg, double* dist, int rows, int T,
               void* stream);
 int segan_llr(const float* ref, const float* deg, double* dist, int rows, int T, int srate,
               void* stream);
+/* STOI, short-time objective intelligibility (Taal et al. 2011; the reference's utils/stoi.m,
+ * DESIGN.md section 10), fp64, of row r = ref / deg [rows][T] restricted to its first lengths[r]
+ * samples (lengths: device int[rows], each in 0 .. T; values outside are clamped; NULL: all T).
+ * srate: 4000 .. 48000 Hz.
+ *   segan_stoi_plan (host only, no device): pq[2] = (p, q), 10000 / srate in lowest terms;
+ *     *ntaps = 2*10*max(p, q) + 1 resampling taps, written to taps when it is not NULL (cap >= *ntaps);
+ *     bands[15][2] (when not NULL) = the DFT bins [lo, hi) of each third-octave band.
+ *     srate 10000: (1, 1), one tap 1.0 (no resampling).
+ *   segan_stoi_dims (host only): the stage sizes for rows of T samples, dims[5] = (Ly resampled
+ *     length, F frames of Ly, Lc compacted length (F - 1)*128 + 256, Fb = F - 1 band frames,
+ *     S = Fb - 29 segments), each 0 where negative.  The buffers of segan_stoi hold
+ *     xr, yr [rows][Ly], energy [rows][F], mask, kept [rows][F] (int), count [rows] (int),
+ *     xs, ys [rows][Lc], X, Y [rows][15][Fb], rho [rows][S][15], d [rows]; each at least one
+ *     element.  Per row: the resampled signals (zero past ceil(len*p/q)), clean frame energies
+ *     in dB, keep mask (1/0), kept frame indices (first count[r] valid), M = count[r], compacted
+ *     signals (zero past (M-1)*128 + 256), band envelopes (first max(M-1, 0) frames valid),
+ *     segment correlations (first max(M-30, 0) segments valid) and d, NaN without segments or
+ *     with a NaN correlation.  Deterministic: no atomics, each row independent of the others. */
+int segan_stoi_plan(int srate, int* pq, int* ntaps, double* taps, int cap, int* bands);
+int segan_stoi_dims(int T, int srate, int* dims);
+int segan_stoi(const float* ref, const float* deg, const int* lengths, int rows, int T, int srate,
+               double* xr, double* yr, double* energy, int* mask, int* kept, int* count,
+               double* xs, double* ys, double* X, double* Y, double* rho, double* d, void* stream);
 
 /* ---- optimizers (model.py:219-228) ---------------------------------------------------- */
 /* torch.optim.RMSprop (no momentum, not centered): sq = alpha*sq + (1-alpha)*g*g;

@@ -14,7 +14,7 @@ PAD_REFLECT = 0
 PAD_ZERO = 1
 ACT_NONE = 0
 ACT_TANH = 1
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 class SeganSrc(Structure):
@@ -96,6 +96,9 @@ SIGNATURES = {
     'segan_ssnr': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_double, _P]),
     'segan_wss': (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     'segan_llr': (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
+    'segan_stoi_plan': (c_int, [c_int, POINTER(c_int), POINTER(c_int), _P, c_int, POINTER(c_int)]),
+    'segan_stoi_dims': (c_int, [c_int, c_int, POINTER(c_int)]),
+    'segan_stoi': (c_int, [_P, _P, _P, c_int, c_int, c_int] + [_P] * 13),
     'segan_rmsprop_step': (c_int, [_P, _P, _P, c_float, c_float, c_float, c_int64, _P]),
     'segan_adam_step': (c_int, [_P, _P, _P, _P, c_float, c_float, c_float, c_float, c_int, c_int64,
                                 _P]),

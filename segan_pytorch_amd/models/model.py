@@ -420,12 +420,16 @@ class SEGAN(Model):
         (quality.composite_eval, utils.py:397-440: 'pesq', 'csig', 'cbak', 'covl', 'wss', 'llr')
         of the enhanced — and with `do_noisy` of the noisy — signal against the clean one.  PESQ
         comes from the external `pesqmain` binary (run in `opts.eval_workers` threads, at most
-        16); without it on PATH pesq / csig / cbak / covl are NaN.  De-emphasis runs along time
-        (the reference applies it along axis 0 of the [B, T] batch, model.py:474-477)."""
+        16); without it on PATH pesq / csig / cbak / covl are NaN.  With `opts.eval_stoi` set (train.py
+        --eval_stoi) a key 'stoi' (quality.stoi, 16 kHz) is added, computed on the same signals.
+        De-emphasis runs along time (the reference applies it along axis 0 of the [B, T] batch,
+        model.py:474-477)."""
         from .. import ops, quality
         self.G.eval()
         self.D.eval()
-        keys = ('ssnr', 'snr', 'pesq', 'csig', 'cbak', 'covl', 'wss', 'llr')
+        with_stoi = bool(getattr(opts, 'eval_stoi', False))
+        keys = ('ssnr', 'snr', 'pesq', 'csig', 'cbak', 'covl', 'wss', 'llr') + (
+            ('stoi',) if with_stoi else ())
         evals = {k: [] for k in keys}
         noisy_evals = {k: [] for k in keys}
         workers = getattr(opts, 'eval_workers', 2)
@@ -446,6 +450,8 @@ class SEGAN(Model):
                     comp = quality.composite_eval(c, d, workers=workers)
                     for k in ('pesq', 'csig', 'cbak', 'covl', 'wss', 'llr'):
                         dst[k] += comp[k].cpu().tolist()
+                    if with_stoi:
+                        dst['stoi'] += quality.stoi(c, d).cpu().tolist()
                 if bidx >= max_samples:
                     break
         self.G.train()

@@ -6,6 +6,7 @@ kernel on ``torch.cuda.current_stream()``.  There is no CPU or ATen fallback: a 
 tensor raises.
 """
 import ctypes
+import operator
 
 import torch
 
@@ -1060,6 +1061,94 @@ def llr(ref, deg, srate=16000):
     """Per-frame log-likelihood ratio of utils.py:598-716 for the rows of ref / deg [rows, T] on
     the device: fp64 [rows, nframes]; NaN where the clean frame is all zeros."""
     return _quality_frames(_lib.load().segan_llr, 'llr', ref, deg, srate)
+
+
+STOI_SRATES = (4000, 48000)
+STOI_BANDS = 15
+
+
+def _stoi_srate(srate):
+    srate_in = srate
+    try:
+        srate = None if isinstance(srate, bool) else operator.index(srate)
+    except TypeError:
+        srate = None
+    if srate is None or not STOI_SRATES[0] <= srate <= STOI_SRATES[1]:
+        raise ValueError('stoi: srate must be an integer from {} to {} Hz, got {!r}'.format(
+            STOI_SRATES[0], STOI_SRATES[1], srate_in))
+    return srate
+
+
+def stoi_plan(srate):
+    """The host-side plan of STOI at `srate` (no device involved): (p, q, taps, bands) with p / q
+    = 10000 / srate in lowest terms, the fp64 CPU tensor of 20 max(p, q) + 1 resampling taps and
+    the int CPU tensor [15, 2] of each third-octave band's DFT bins [lo, hi)."""
+    srate = _stoi_srate(srate)
+    lib = _lib.load()
+    pq, n, bands = (ctypes.c_int * 2)(), ctypes.c_int(), (ctypes.c_int * (2 * STOI_BANDS))()
+    check(lib.segan_stoi_plan(srate, pq, ctypes.byref(n), None, 0, None), 'stoi_plan')
+    taps = torch.empty(n.value, dtype=torch.float64)
+    check(lib.segan_stoi_plan(srate, pq, ctypes.byref(n), _ptr(taps), n.value, bands), 'stoi_plan')
+    return pq[0], pq[1], taps, torch.tensor(list(bands), dtype=torch.int64).view(STOI_BANDS, 2)
+
+
+def _stoi_lengths(lengths, rows, T, device):
+    lens = torch.as_tensor(lengths).detach().cpu()
+    if lens.dim() != 1 or lens.numel() != rows or lens.dtype.is_floating_point or lens.dtype in (
+            torch.bool, torch.complex64, torch.complex128):
+        raise ValueError('stoi: lengths must hold {} integers, got {}'.format(rows, lengths))
+    if rows and (int(lens.min()) < 0 or int(lens.max()) > T):
+        raise ValueError('stoi: lengths must lie in 0 .. {}, got {}'.format(T, lens.tolist()))
+    return lens.to(dtype=torch.int32).to(device)
+
+
+def stoi_stages(ref, deg, srate=16000, lengths=None):
+    """STOI (Taal et al.'s short-time objective intelligibility) of each
+    row of ref / deg [rows, T] with every intermediate, fp64, on the device.  Row r is the signal
+    ref[r, :lengths[r]] (all T without `lengths`; host integers, a CUDA tensor is copied to the
+    host to be checked).  Returns a dict of device tensors, sized for T, of which each row uses
+    its own leading part: xr, yr [rows, Ly] (resampled to 10 kHz), energy, mask, kept
+    [rows, F] (clean frame energies in dB, keep mask, kept frame indices), count [rows] (M),
+    xs, ys [rows, Lc] (compacted), X, Y [rows, 15, Fb] (band envelopes), rho [rows, S, 15]
+    (segment correlations), d [rows]; and dims = (Ly, F, Lc, Fb, S)."""
+    _chk(ref, 'ref', 2)
+    _chk(deg, 'deg', 2)
+    if ref.shape != deg.shape:
+        raise ValueError('stoi: shapes differ {} vs {}'.format(tuple(ref.shape), tuple(deg.shape)))
+    srate = _stoi_srate(srate)
+    rows, T = ref.shape
+    lens = None if lengths is None else _stoi_lengths(lengths, rows, T, ref.device)
+    lib = _lib.load()
+    dims = (ctypes.c_int * 5)()
+    check(lib.segan_stoi_dims(T, srate, dims), 'stoi')
+    Ly, F, Lc, Fb, S = list(dims)
+    f64 = dict(device=ref.device, dtype=torch.float64)
+    i32 = dict(device=ref.device, dtype=torch.int32)
+    xr = torch.empty((2, rows, max(Ly, 1)), **f64)
+    energy = torch.empty((rows, max(F, 1)), **f64)
+    mask = torch.empty((rows, max(F, 1)), **i32)
+    kept = torch.empty((rows, max(F, 1)), **i32)
+    count = torch.empty(rows, **i32)
+    xs = torch.empty((2, rows, max(Lc, 1)), **f64)
+    env = torch.empty((2, rows, STOI_BANDS, max(Fb, 1)), **f64)
+    rho = torch.empty((rows, max(S, 1), STOI_BANDS), **f64)
+    d = torch.empty(rows, **f64)
+    check(lib.segan_stoi(_ptr(ref), _ptr(deg), _ptr(lens), rows, T, srate, _ptr(xr[0]), _ptr(xr[1]),
+                         _ptr(energy), _ptr(mask), _ptr(kept), _ptr(count), _ptr(xs[0]),
+                         _ptr(xs[1]), _ptr(env[0]), _ptr(env[1]), _ptr(rho), _ptr(d), _stream()),
+          'stoi')
+    return dict(xr=xr[0, :, :Ly], yr=xr[1, :, :Ly], energy=energy[:, :F], mask=mask[:, :F],
+                kept=kept[:, :F], count=count, xs=xs[0, :, :Lc], ys=xs[1, :, :Lc],
+                X=env[0, :, :, :Fb], Y=env[1, :, :, :Fb], rho=rho[:, :S], d=d,
+                dims=(Ly, F, Lc, Fb, S))
+
+
+def stoi(ref, deg, srate=16000, lengths=None):
+    """STOI of each row of ref / deg [rows, T] (fp32 CUDA tensors) on the device: fp64 [rows],
+    NaN where it is undefined (a clean signal of digital silence, fewer than 30 band frames after
+    silent-frame removal, a 0/0 correlation).  `lengths`: optional per-row valid sample counts
+    (see stoi_stages).  srate: any integer from 4000 to 48000 Hz.  No device-to-host copy."""
+    return stoi_stages(ref, deg, srate, lengths)['d']
 
 
 def rmsprop_step(p, g, sq, lr, alpha, eps):

@@ -1,5 +1,6 @@
 """Objective speech-quality evaluation of the reference's segan/utils.py:299-440 on the device:
-CSIG / CBAK / COVL (Hu & Loizou's composite measures) from WSS, LLR, segmental SNR and PESQ.
+CSIG / CBAK / COVL (Hu & Loizou's composite measures) from WSS, LLR, segmental SNR and PESQ, and
+STOI (Taal et al.'s short-time objective intelligibility, the reference's utils/stoi.m).
 
 The per-frame measures are HIP kernels (``ops.wss``, ``ops.llr``, ``ops.ssnr``); the trimmed means
 and the three linear formulas are a few hundred numbers per row and run as torch ops on the device.
@@ -171,3 +172,21 @@ def composite_eval(ref, deg, pesq=None, workers=2):
     covl = (1.594 + 0.805 * pesq_t - 0.512 * llr_m - 0.007 * wss_m).clamp(1, 5)
     return {'csig': csig, 'cbak': cbak, 'covl': covl, 'pesq': pesq_t, 'ssnr': ssnr_m,
             'wss': wss_m, 'llr': llr_m}
+
+
+def stoi(ref, deg, srate=SRATE, lengths=None):
+    """STOI of each row of ref / deg ([rows, T] or [T] CUDA tensors of the same shape) on the
+    device: fp64 tensor [rows].  srate: any integer from 4000 to 48000 Hz (resampled to 10 kHz on
+    the device).  `lengths`: optional per-row valid sample counts, so that signals of different
+    lengths go through one call padded to a common T (row r is ref[r, :lengths[r]]).
+
+    Unlike composite_eval, which truncates to the common length, ref and deg of different
+    lengths raise ValueError, as stoi.m does.  NaN where STOI is undefined: a clean signal of
+    digital silence, fewer than 30 band frames (about 0.4 s of non-silent speech) or a 0/0
+    correlation."""
+    ref = _as_rows(ref, 'ref')
+    deg = _as_rows(deg, 'deg')
+    if ref.shape != deg.shape:
+        raise ValueError('stoi: ref {} and deg {} differ in shape (signals of different lengths '
+                         'are not compared)'.format(tuple(ref.shape), tuple(deg.shape)))
+    return ops.stoi(ref.float().contiguous(), deg.float().contiguous(), srate, lengths)

@@ -57,6 +57,9 @@ FLAGS = [
     ('--preemph', dict(type=float, default=0.95)),
     ('--max_samples', dict(type=int, default=None)),
     ('--eval_workers', dict(type=int, default=2)),
+    ('--eval_stoi', dict(action='store_true', default=False,
+                         help='the evaluation also reports STOI (short-time objective '
+                              'intelligibility); the validation objective stays SSNR')),
     ('--slice_workers', dict(type=int, default=1)),
     ('--num_workers', dict(type=int, default=1)),
     ('--no-cuda', dict(action='store_true', default=False)),
