@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SEGAN_ABI_VERSION 15
+#define SEGAN_ABI_VERSION 16
 
 #define SEGAN_PAD_REFLECT 0
 #define SEGAN_PAD_ZERO 1
@@ -325,7 +325,9 @@ int segan_conv1d_dgrad_short(const float* da, const float* wg, float* dx, int B,
 /* Global pooling over time of x[rows][L] (rows = B*C), the 'gmax' / 'gavg' discriminator heads
  * (discriminator.py:128-137,183-190).  mode 0: y[row] = max, idx[row] = the FIRST position
  * attaining it; mode 1: y[row] = mean (idx unused, may be NULL).  bwd: dx[row][t] =
- * (t == idx[row]) ? dy[row] : 0, or dy[row] / L. */
+ * (t == idx[row]) ? dy[row] : 0, or dy[row] / L.  Rows of -inf give -inf at index 0; the maximum
+ * of a row that contains NaN is unspecified (AdaptiveMaxPool1d propagates the NaN; this kernel
+ * keeps one only where it is the first element a lane visits): activations here are finite. */
 int segan_pool_time_fwd(const float* x, float* y, int* idx, int rows, int L, int mode,
                         void* stream);
 int segan_pool_time_bwd(const float* dy, const int* idx, float* dx, int rows, int L, int mode,
@@ -433,9 +435,11 @@ int segan_stoi(const float* ref, const float* deg, const int* lengths, int rows,
  * p -= lr * g / (sqrt(sq) + eps), over a flat arena of n floats. */
 int segan_rmsprop_step(float* p, const float* g, float* sq, float lr, float alpha, float eps,
                        int64_t n, void* stream);
-/* torch.optim.Adam without weight decay/amsgrad; `step` is the 1-based step count. */
-int segan_adam_step(float* p, const float* g, float* m, float* v, float lr, float beta1,
-                    float beta2, float eps, int step, int64_t n, void* stream);
+/* torch.optim.Adam without weight decay/amsgrad; `step` is the 1-based step count.  The betas
+ * are doubles because torch forms 1 - beta and the bias corrections in double: 1 - beta2 taken
+ * from an fp32 0.999 is 1.3e-5 off, and exp_avg_sq with it. */
+int segan_adam_step(float* p, const float* g, float* m, float* v, float lr, double beta1,
+                    double beta2, float eps, int step, int64_t n, void* stream);
 int segan_fill(float* p, float value, int64_t n, void* stream);
 int segan_scale(float* p, float s, int64_t n, void* stream);
 

@@ -14,7 +14,7 @@ PAD_REFLECT = 0
 PAD_ZERO = 1
 ACT_NONE = 0
 ACT_TANH = 1
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 
 class SeganSrc(Structure):
@@ -100,7 +100,7 @@ SIGNATURES = {
     'segan_stoi_dims': (c_int, [c_int, c_int, POINTER(c_int)]),
     'segan_stoi': (c_int, [_P, _P, _P, c_int, c_int, c_int] + [_P] * 13),
     'segan_rmsprop_step': (c_int, [_P, _P, _P, c_float, c_float, c_float, c_int64, _P]),
-    'segan_adam_step': (c_int, [_P, _P, _P, _P, c_float, c_float, c_float, c_float, c_int, c_int64,
+    'segan_adam_step': (c_int, [_P, _P, _P, _P, c_float, c_double, c_double, c_float, c_int, c_int64,
                                 _P]),
     'segan_fill': (c_int, [_P, c_float, c_int64, _P]),
     'segan_scale': (c_int, [_P, c_float, c_int64, _P]),

@@ -849,13 +849,15 @@ extern "C" int segan_rmsprop_step(float* p, const float* g, float* sq, float lr,
 
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                             float* __restrict__ m, float* __restrict__ v, float step_size,
-                            float beta1, float beta2, float eps, float inv_sqrt_bc2, size_t n) {
+                            float omb1, float beta2, float omb2, float eps, float inv_sqrt_bc2,
+                            size_t n) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n;
        i += (size_t)gridDim.x * blockDim.x) {
     const float gv = g[i];
-    // torch: exp_avg.lerp_(grad, 1-beta1); exp_avg_sq = beta2*v + (1-beta2)*g*g
-    const float mv = m[i] + (gv - m[i]) * (1.0f - beta1);
-    const float vv = beta2 * v[i] + (1.0f - beta2) * gv * gv;
+    // torch: exp_avg.lerp_(grad, 1-beta1); exp_avg_sq = beta2*v + (1-beta2)*g*g, with
+    // omb = 1 - beta taken in double on the host as torch takes it (1.0f - 0.999f is 1.3e-5 off)
+    const float mv = m[i] + (gv - m[i]) * omb1;
+    const float vv = beta2 * v[i] + omb2 * gv * gv;
     m[i] = mv;
     v[i] = vv;
     const float denom = sqrtf(vv) * inv_sqrt_bc2 + eps;
@@ -863,16 +865,18 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
   }
 }
 
-extern "C" int segan_adam_step(float* p, const float* g, float* m, float* v, float lr, float beta1,
-                               float beta2, float eps, int step, int64_t n, void* stream) {
+extern "C" int segan_adam_step(float* p, const float* g, float* m, float* v, float lr,
+                               double beta1, double beta2, float eps, int step, int64_t n,
+                               void* stream) {
   SEGAN_REQUIRE(p && g && m && v && n > 0 && step >= 1, "adam_step: bad arguments");
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  const double bc1 = 1.0 - pow(beta1, (double)step);
+  const double bc2 = 1.0 - pow(beta2, (double)step);
   const float step_size = (float)((double)lr / bc1);
   const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
   int blocks = (int)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256);
   hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
-                     step_size, beta1, beta2, eps, inv_sqrt_bc2, (size_t)n);
+                     step_size, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), eps,
+                     inv_sqrt_bc2, (size_t)n);
   return segan_check_launch("adam_step");
 }
 

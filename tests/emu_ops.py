@@ -22,14 +22,26 @@ _saved = {}
 def _mat(src):
     """Materialise a Src: concat + per-channel affine + PReLU, in float64."""
     x = src.t0 if src.t1 is None else torch.cat((src.t0, src.t1), 1)
+    return _xform(x, src.scale, src.shift, src.slope)
+
+
+def _xform(x, scale, shift, slope):
+    """prelu(x * scale[c] + shift[c], slope[c]) in float64; every vector may be None."""
     x = x.double()
-    if src.scale is not None:
-        x = x * src.scale.detach().double().view(1, -1, 1)
-    if src.shift is not None:
-        x = x + src.shift.detach().double().view(1, -1, 1)
-    if src.slope is not None:
-        x = torch.where(x > 0, x, x * src.slope.detach().double().view(1, -1, 1))
+    if scale is not None:
+        x = x * scale.detach().double().view(1, -1, 1)
+    if shift is not None:
+        x = x + shift.detach().double().view(1, -1, 1)
+    if slope is not None:
+        x = torch.where(x > 0, x, x * slope.detach().double().view(1, -1, 1))
     return x
+
+
+def _vec(v, C, fill):
+    """A per-channel parameter as float64 [1, C, 1]; None = the kernel's default `fill`."""
+    if v is None:
+        return torch.full((1, C, 1), fill, dtype=torch.float64)
+    return v.detach().double().view(1, -1, 1)
 
 
 def _conv(x, w, b, S, roll, mode, padL):
@@ -106,8 +118,9 @@ def bn_stats(x, gamma, beta, eps, momentum, running_mean, running_var):
     mean = xd.mean((0, 2))
     var = xd.var((0, 2), unbiased=False)
     rstd = (var + eps).rsqrt()
-    scale = gamma.detach().double() * rstd
-    shift = beta.detach().double() - mean * scale
+    C = x.shape[1]
+    scale = _vec(gamma, C, 1.0).view(-1) * rstd
+    shift = _vec(beta, C, 0.0).view(-1) - mean * scale
     if running_mean is not None:
         running_mean.mul_(1 - momentum).add_(momentum * mean.float())
         running_var.mul_(1 - momentum).add_(momentum * (var * n / max(n - 1, 1)).float())
@@ -137,8 +150,9 @@ def bn_final(ws_all, gamma, beta, eps, momentum, running_mean, running_var):
         n = tot
     var = m2 / n
     rstd = (var + eps).rsqrt()
-    scale = gamma.detach().double() * rstd
-    shift = beta.detach().double() - mean * scale
+    C = w.shape[1]
+    scale = _vec(gamma, C, 1.0).view(-1) * rstd
+    shift = _vec(beta, C, 0.0).view(-1) - mean * scale
     if running_mean is not None:
         running_mean.mul_(1 - momentum).add_(momentum * mean.float())
         running_var.mul_(1 - momentum).add_(momentum * (m2 / (n - 1).clamp_min(1)).float())
@@ -149,8 +163,8 @@ def _bn_bwd_terms(a, dh, slope, bn):
     mean, rstd, gamma, beta = bn
     ad = a.double()
     mu, rs = mean.double().view(1, -1, 1), rstd.double().view(1, -1, 1)
-    ga, be = gamma.detach().double().view(1, -1, 1), beta.detach().double().view(1, -1, 1)
-    sl = slope.detach().double().view(1, -1, 1)
+    C = a.shape[1]
+    ga, be, sl = _vec(gamma, C, 1.0), _vec(beta, C, 0.0), _vec(slope, C, 1.0)
     xh = (ad - mu) * rs
     v = ga * xh + be
     dhd = dh.double()
@@ -176,11 +190,11 @@ def act_bwd_bn_apply(a, dh, slope, bn, totals, count_total, dbias=None, ws=None)
 
 
 def affine_prelu(x, scale=None, shift=None, slope=None):
-    return _mat(ops.Src(x, scale=scale, shift=shift, slope=slope)).float()
+    return _xform(x, scale, shift, slope).float()
 
 
 def affine_tanh(x, scale=None, shift=None):
-    return torch.tanh(_mat(ops.Src(x, scale=scale, shift=shift))).float()
+    return torch.tanh(_xform(x, scale, shift, None)).float()
 
 
 def scale_mask(x, scale, mask):
@@ -216,8 +230,10 @@ def pool_time_bwd(dy, idx, L, mode):
 
 
 def bce_logits_const(x, target):
-    t = torch.full_like(x.double(), target)
-    return F.binary_cross_entropy_with_logits(x.double(), t).float()
+    # max(x, 0) - x t + log1p(exp(-|x|)), the form of the header: torch's own float64 kernel takes
+    # log(1 + exp(-|x|)), which is 1 % off where the loss is 1e-13 (x = -30 against target 0)
+    xd = x.double()
+    return (xd.clamp_min(0) - xd * target + torch.log1p(torch.exp(-xd.abs()))).mean().float()
 
 
 def bce_logits_const_bwd(x, target, gout=None, gscale=1.0):
@@ -248,8 +264,7 @@ def act_bwd(a, dh, dskip=None, slope=None, alpha=None, bn=None, dslope=None, dal
         return g.float()
     mean, rstd, gamma, beta = bn
     mu, rs = mean.double().view(1, -1, 1), rstd.double().view(1, -1, 1)
-    ga = gamma.detach().double().view(1, -1, 1)
-    be = beta.detach().double().view(1, -1, 1)
+    ga, be = _vec(gamma, a.shape[1], 1.0), _vec(beta, a.shape[1], 0.0)
     xh = (ad - mu) * rs
     v = ga * xh + be
     # slope None = no activation behind the BatchNorm (the kernel's slope defaults to 1)
