@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SEGAN_ABI_VERSION 16
+#define SEGAN_ABI_VERSION 17
 
 #define SEGAN_PAD_REFLECT 0
 #define SEGAN_PAD_ZERO 1
@@ -429,6 +429,47 @@ int segan_stoi_dims(int T, int srate, int* dims);
 int segan_stoi(const float* ref, const float* deg, const int* lengths, int rows, int T, int srate,
                double* xr, double* yr, double* energy, int* mask, int* kept, int* count,
                double* xs, double* ys, double* X, double* Y, double* rho, double* d, void* stream);
+
+/* ---- on-the-fly additive noise (the reference's Additive, utils.py:43-297)
+ * fp64 arithmetic on fp32 rows x / clean [rows][T], row r restricted to its first lengths[r]
+ * samples (device int[rows], clamped to 0 .. T; NULL: all T).  One workgroup per row, no atomics:
+ * a row's result depends on neither the other rows nor its position.
+ *   segan_asl_p56: ITU-T P.56 method-B active speech level (utils.py:180-297).  Envelope q = two
+ *     cascaded filters y[n] = (1-g)|x[n]| + g y[n-1], g = exp(-1/(0.03 srate)); thresholds c_j =
+ *     2^(j-15), j = 0 .. nbits-2; counts[r][j] = samples at most ceil(0.2 srate) after a sample
+ *     with q >= c_j (the reference's hangover loop); then the reference's finalisation and
+ *     bin_interp, bounded to 1000 iterations.  nbits must be 16 (otherwise -3, unsupported).
+ *     level[rows][4] = (sq = sum x^2, asl_ms, asl, c0), c0 NaN and asl_ms = asl = 0 where the
+ *     reference returns (0, 0, None); counts int[rows][15]; status int[rows], bit 0 = iteration
+ *     cap reached; q (optional, may be NULL) double[rows][T], zero past the row's length.
+ *   segan_additive_mix (utils.py:98-134 and 89-95): segment = bank[starts[r] .. + len) of the flat
+ *     fp32 noise bank of n_bank samples, Pn = its mean square, sf = sqrt(px[r] / Pn /
+ *     10^(snr_db[r]/10)), v = clean + sf*segment; while max(v) >= 1 or min(v) < -1 every sample is
+ *     divided by 1.1, then 1.2, ... (n successive fp64 divisions), then rounded to fp32 once.
+ *     starts int64[rows], snr_db / px double[rows] are device arrays.  prev / prev_out (both or
+ *     neither): float[rows], the clean sample preceding each row, mixed with bank[starts[r] - 1]
+ *     and divided the same way (for a pre-emphasis that follows).  noisy[rows][T] (clean past the
+ *     row's length); info double[rows][2] = (Pn, sf); istat int[rows][2] = (n, status): bit 0 =
+ *     division cap (1000) reached, bit 1 = Pn == 0, bit 2 = segment (or starts[r] - 1 with prev)
+ *     outside the bank; with bit 1 or 2 sf = 0 and the bank is not read.  px == 0 gives sf = 0. */
+int segan_asl_p56(const float* x, const int* lengths, int rows, int T, int srate, int nbits,
+                  double* level, int* counts, int* status, double* q, void* stream);
+int segan_additive_mix(const float* clean, const int* lengths, const float* bank, int64_t n_bank,
+                       const int64_t* starts, const double* snr_db, const double* px,
+                       const float* prev, int rows, int T, float* noisy, float* prev_out,
+                       double* info, int* istat, void* stream);
+/* The mixer inside the pcm16 loader.  index (device int[n], NULL: 0 .. n-1) names the batch items
+ * 0 .. B-1 that rows 0 .. n-1 stand for; n <= 65535.
+ *   segan_pcm16_wave: wave[n][T] = the clean row of pcm[B][2][T+1] (segan_pcm16_prep's layout)
+ *     normalised (2/65535)(x-32767)+1 and rounded to fp32, prev[n] = the same of the row's
+ *     element 0 (the wav sample preceding the slice);
+ *   segan_preemph_rows: y[index[k]][t] = x[k][t] - coef*x[k][t-1] (x[k][-1] = prev[k]) in double,
+ *     rounded once; y[.][0] = x[k][0] where first[index[k]] is set; coef <= 0 copies.  x [n][T],
+ *     y [B][T]: only the indexed rows of y are written. */
+int segan_pcm16_wave(const int16_t* pcm, const int* index, float* wave, float* prev, int n, int B,
+                     int T, void* stream);
+int segan_preemph_rows(const float* x, const float* prev, const unsigned char* first,
+                       const int* index, float* y, int n, int B, int T, double coef, void* stream);
 
 /* ---- optimizers (model.py:219-228) ---------------------------------------------------- */
 /* torch.optim.RMSprop (no momentum, not centered): sq = alpha*sq + (1-alpha)*g*g;

@@ -7,6 +7,9 @@ time per batch with bench.py's step on resident synthetic data.  Checkpoint writ
 per-batch timing (the reference's `btime` excludes them too: model.py:322-348).
 
     python scripts/train_loop_bench.py [--items 3000] [--epochs 6]  > profiles/rNN_train_loop.json
+
+`--additive` (opt-in) adds `--additive_noises` over two synthetic 30 s noise wavs: every item's noisy
+row is mixed on the loader's side stream.
 """
 import argparse
 import json
@@ -25,6 +28,8 @@ ap.add_argument('--items', type=int, default=3000)
 ap.add_argument('--epochs', type=int, default=6)
 ap.add_argument('--batch', type=int, default=300)
 ap.add_argument('--tmp', default='/tmp/segan_train_loop')
+ap.add_argument('--additive', action='store_true',
+                help='mix noise into every item on the fly (train.py --additive_noises)')
 args = ap.parse_args()
 
 os.makedirs(args.tmp, exist_ok=True)
@@ -39,6 +44,16 @@ from segan_pytorch_amd.datasets import SHARD_MAGIC
 json.dump({'magic': SHARD_MAGIC, 'n_items': args.items, 'slice_size': T,
            'names': ['utt_{}'.format(i) for i in range(args.items)],
            'slice_idx': [0] * args.items, 'first': [0] * args.items}, open(prefix + '.json', 'w'))
+
+extra = []
+if args.additive:
+    from scipy.io import wavfile
+    ndir = os.path.join(args.tmp, 'noises')
+    os.makedirs(ndir, exist_ok=True)
+    for i in range(2):
+        wavfile.write(os.path.join(ndir, 'n{}.wav'.format(i)), 16000,
+                      (rng.randn(30 * 16000) * 1500).astype(np.int16))
+    extra = ['--additive_noises', ndir]
 
 import train
 from segan_pytorch_amd.models import core
@@ -66,7 +81,7 @@ core.Model.save = lambda self, *a, **k: None
 opts = train.build_parser().parse_args(
     ['--pcm_shard', prefix, '--batch_size', str(args.batch), '--epoch', str(args.epochs),
      '--save_path', os.path.join(args.tmp, 'ckpt'), '--no_train_gen', '--save_freq', '1000',
-     '--num_workers', '2'])
+     '--num_workers', '2'] + extra)
 opts.bias = not opts.no_bias
 os.makedirs(opts.save_path, exist_ok=True)
 train.main(opts)
@@ -77,7 +92,7 @@ ms = 1e3 * (t1 - state['t0']) / timed
 out = {'what': 'train.py --pcm_shard (default SEGAN+ net, batch {}, RMSprop, host z, int16 shard '
                'through worker gathers + GPU prep): {} epochs of {} batches, the first epoch is '
                'warm-up, device-synchronised clock around the rest'.format(args.batch, args.epochs, per_epoch),
-       'ms_per_batch': ms, 'chunks_per_s': args.batch * 1e3 / ms, 'batches_timed': timed}
+       'additive': bool(args.additive), 'ms_per_batch': ms, 'chunks_per_s': args.batch * 1e3 / ms, 'batches_timed': timed}
 try:
     import glob
     b = json.load(open(sorted(glob.glob(os.path.join(ROOT, 'profiles', 'r[0-9][0-9]_bench_line.json')))[-1]))

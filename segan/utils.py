@@ -1,12 +1,15 @@
 """Import-compatibility alias of the reference's objective evaluation helpers (segan/utils.py):
-numpy in, numpy / python values out, computed on the MI355X by segan_pytorch_amd.quality.  Only
-the composite-evaluation names are provided."""
+numpy in, numpy / python values out, computed on the MI355X by segan_pytorch_amd.quality, and of
+its additive-noise mixer (`Additive`, `ComposeAdditive`: segan_pytorch_amd.augment)."""
 import numpy as _np
 import torch as _torch
 
 from segan_pytorch_amd import ops as _ops
 from segan_pytorch_amd import quality as _q
+from segan_pytorch_amd.augment import Additive, ComposeAdditive  # noqa: F401
 
+# the evaluation names; Additive / ComposeAdditive are imported by name (`from segan.utils import
+# Additive`), as the reference's train.py does
 __all__ = ['CompositeEval', 'eval_composite', 'SSNR', 'wss', 'llr', 'PESQ']
 
 

@@ -14,7 +14,7 @@ PAD_REFLECT = 0
 PAD_ZERO = 1
 ACT_NONE = 0
 ACT_TANH = 1
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 
 class SeganSrc(Structure):
@@ -99,6 +99,10 @@ SIGNATURES = {
     'segan_stoi_plan': (c_int, [c_int, POINTER(c_int), POINTER(c_int), _P, c_int, POINTER(c_int)]),
     'segan_stoi_dims': (c_int, [c_int, c_int, POINTER(c_int)]),
     'segan_stoi': (c_int, [_P, _P, _P, c_int, c_int, c_int] + [_P] * 13),
+    'segan_asl_p56': (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
+    'segan_additive_mix': (c_int, [_P, _P, _P, c_int64, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P]),
+    'segan_pcm16_wave': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    'segan_preemph_rows': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_double, _P]),
     'segan_rmsprop_step': (c_int, [_P, _P, _P, c_float, c_float, c_float, c_int64, _P]),
     'segan_adam_step': (c_int, [_P, _P, _P, _P, c_float, c_double, c_double, c_float, c_int, c_int64,
                                 _P]),

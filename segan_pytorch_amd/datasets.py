@@ -258,8 +258,14 @@ class PCMShardLoader(object):
     (a RandomSampler seeded from torch's global generator), or a DistributedSampler per rank."""
 
     def __init__(self, shard, batch_size, preemph, device, sampler=None, drop_last=False,
-                 num_workers=2):
+                 num_workers=2, additive=None, additive_prob=1.0, additive_seed=None,
+                 record_additive=False):
         from torch.utils.data import RandomSampler
+        if additive is not None and not 0.0 <= float(additive_prob) <= 1.0:
+            raise ValueError('additive_prob must lie in 0 .. 1, got {}'.format(additive_prob))
+        self.additive, self.additive_prob = additive, float(additive_prob)
+        self.additive_rng = np.random.default_rng(additive_seed)
+        self.additive_records = [] if record_additive else None
         self.shard = shard
         self.sampler = sampler if sampler is not None else RandomSampler(shard)
         self.preemph = float(preemph)
@@ -284,9 +290,40 @@ class PCMShardLoader(object):
     def _prep(self, item):
         from . import ops
         names, pcm, first, idx = item
-        clean, noisy = ops.pcm16_prep(pcm.to(self.device, non_blocking=True),
-                                      first.to(self.device, non_blocking=True), self.preemph)
+        pcm_d = pcm.to(self.device, non_blocking=True)
+        first_d = first.to(self.device, non_blocking=True)
+        clean, noisy = ops.pcm16_prep(pcm_d, first_d, self.preemph)
+        if self.additive is not None:
+            names = self._add_noise(names, pcm_d, first_d, noisy)
         return [names, clean, noisy, idx]
+
+    def _add_noise(self, names, pcm_d, first_d, noisy):
+        """On-the-fly additive noise (augment.Additive): each item is
+        selected with probability `additive_prob`; a selected item's noisy row becomes clean +
+        noise and its name gets '_additive' appended (WSEGAN's masked regression term applies to
+        exactly those).  Per selected slice: the wave is the fp32 min-max-normalised clean slice
+        of T samples; the P.56 level, the noise power and the clipping test are taken over those T
+        samples, at 16 kHz; the noise segment starts at s >= 1 of its file.  When the slice does not start
+        its wav, the pre-emphasis of the mixed row needs the sample preceding the slice: it is
+        (clean_prev + sf * noise[s-1]) followed by the slice's own anti-clipping divisions,
+        rounded to fp32; when it does, y[0] = x[0].  The pre-emphasis is computed in double and
+        rounded once, like the unaugmented rows.  Runs on the stream `_prep` runs on (the
+        loader's side stream), between the H2D copy and the consumer; `clean` is untouched."""
+        from . import ops
+        B, T = noisy.shape
+        sel = np.nonzero(self.additive_rng.random(B) < self.additive_prob)[0]
+        if len(sel) == 0:
+            if self.additive_records is not None:
+                self.additive_records.append(None)
+            return names
+        wave, prev = ops.pcm16_wave(pcm_d, sel)
+        mixed, info = self.additive.mix(wave, generator=self.additive_rng, prev=prev)
+        ops.preemph_rows(mixed, info['prev'], first_d, noisy, self.preemph, sel)
+        if self.additive_records is not None:
+            info.update(index=sel, wave=wave, wave_prev=prev, mixed=mixed)
+            self.additive_records.append(info)
+        chosen = set(sel.tolist())
+        return [n + '_additive' if i in chosen else n for i, n in enumerate(names)]
 
     def _stage(self, item):
         """H2D copy + prep kernel of one batch on the loader's SIDE stream; (batch, event)."""

@@ -1151,6 +1151,176 @@ def stoi(ref, deg, srate=16000, lengths=None):
     return stoi_stages(ref, deg, srate, lengths)['d']
 
 
+ASL_THRESHOLDS = 15      # nbits - 1 thresholds 2^-15 .. 2^-1 (nbits = 16)
+ADDITIVE_CAP = 1         # status bits of asl_p56 / additive_mix (include/segan_hip.h)
+ADDITIVE_PN0 = 2
+ADDITIVE_RANGE = 4
+
+
+def _int_arg(v, what, lo, hi):
+    try:
+        out = None if isinstance(v, bool) else operator.index(v)
+    except TypeError:
+        out = None
+    if out is None or not lo <= out <= hi:
+        raise ValueError('{} must be an integer from {} to {}, got {!r}'.format(what, lo, hi, v))
+    return out
+
+
+def asl_p56_stages(x, srate=16000, nbits=16, lengths=None, _want_q=True):
+    """ITU-T P.56 method-B active speech level of each row of x [rows, T] (fp32 CUDA tensor), the
+    reference's `Additive.asl_P56` (utils.py:180-297) in fp64 on the device.
+    Row r is x[r, :lengths[r]] (all T without `lengths`; host integers as in `stoi_stages`).
+    Returns a dict of device tensors: sq [rows] (sum of squares), asl_ms (active-level mean
+    square), asl (activity factor), c0 (threshold; NaN where the reference returns None, and then
+    asl_ms = asl = 0), counts int32 [rows, 15] (activity counts per threshold 2^-15 .. 2^-1),
+    status int32 [rows] (1: the interpolation's iteration cap was reached) and q fp64 [rows, T]
+    (the envelope, zero past the row's length).  nbits must be 16."""
+    _chk(x, 'x', 2)
+    srate = _int_arg(srate, 'asl_p56: srate', 1, 768000)
+    if _int_arg(nbits, 'asl_p56: nbits', 2, 64) != ASL_THRESHOLDS + 1:
+        raise NotImplementedError('asl_p56: nbits={} is not supported (16 only)'.format(nbits))
+    rows, T = x.shape
+    if rows == 0 or T == 0:
+        raise ValueError('asl_p56: empty input {}'.format(tuple(x.shape)))
+    lens = None if lengths is None else _stoi_lengths(lengths, rows, T, x.device)
+    level = torch.empty((rows, 4), device=x.device, dtype=torch.float64)
+    counts = torch.empty((rows, ASL_THRESHOLDS), device=x.device, dtype=torch.int32)
+    status = torch.empty(rows, device=x.device, dtype=torch.int32)
+    q = torch.empty((rows, T), device=x.device, dtype=torch.float64) if _want_q else None
+    check(_lib.load().segan_asl_p56(_ptr(x), _ptr(lens), rows, T, srate, ASL_THRESHOLDS + 1,
+                                    _ptr(level), _ptr(counts), _ptr(status), _ptr(q), _stream()),
+          'asl_p56')
+    out = dict(sq=level[:, 0], asl_ms=level[:, 1], asl=level[:, 2], c0=level[:, 3], counts=counts,
+               status=status)
+    if _want_q:
+        out['q'] = q
+    return out
+
+
+def asl_p56(x, srate=16000, nbits=16, lengths=None):
+    """`asl_p56_stages` without the envelope: dict(sq, asl_ms, asl, c0, counts, status) of device
+    tensors.  No device-to-host copy."""
+    return asl_p56_stages(x, srate, nbits, lengths, _want_q=False)
+
+
+def _host_vec(v, rows, dtype, what):
+    t = torch.as_tensor(v).detach().cpu().reshape(-1)
+    if t.numel() != rows:
+        raise ValueError('additive_mix: {} must hold {} values, got {}'.format(what, rows, t.numel()))
+    if dtype == torch.int64 and (t.dtype.is_floating_point or t.dtype == torch.bool):
+        raise ValueError('additive_mix: {} must be integers'.format(what))
+    return t.to(dtype)
+
+
+def additive_mix(clean, bank, starts, snrs, px, lengths=None, prev=None):
+    """clean [rows, T] + noise at a target SNR, the reference's `addnoise_asl` and anti-clipping
+    loop (utils.py:98-134, 89-95) in fp64 on the device, rounded to fp32 once.  bank: the flat
+    fp32 CUDA noise bank; starts (host integers [rows]): absolute index of each row's segment,
+    checked here to lie inside the bank; snrs (host numbers [rows]): dB; px: fp64 CUDA tensor
+    [rows], the rows' asl_ms from `asl_p56`.  prev (optional fp32 CUDA [rows]): the clean sample
+    preceding each row; it is mixed with bank[start - 1] (start >= 1) and returned as
+    info['prev'].  Returns (noisy [rows, T], info) with info = dict(Pn, sf fp64 [rows], n,
+    status int32 [rows]): noise mean square, scale factor, number of anti-clipping divisions;
+    status: ADDITIVE_CAP (the division cap was reached) | ADDITIVE_PN0 (a segment of digital
+    silence: sf = 0, noisy == clean).  px == 0 gives sf = 0 and noisy == clean."""
+    _chk(clean, 'clean', 2)
+    _chk(bank, 'bank', 1)
+    rows, T = clean.shape
+    if rows == 0 or T == 0 or bank.numel() == 0:
+        raise ValueError('additive_mix: empty input')
+    if not (isinstance(px, torch.Tensor) and px.is_cuda and px.dtype == torch.float64 and
+            px.numel() == rows):
+        raise TypeError('additive_mix: px must be a CUDA float64 tensor of {} values'.format(rows))
+    if bank.device != clean.device or px.device != clean.device:
+        raise ValueError('additive_mix: tensors on different devices')
+    st = _host_vec(starts, rows, torch.int64, 'starts')
+    sn = _host_vec(snrs, rows, torch.float64, 'snrs')
+    lens = None if lengths is None else _stoi_lengths(lengths, rows, T, clean.device)
+    need = torch.full((rows,), T, dtype=torch.int64) if lens is None else lens.cpu().to(torch.int64)
+    lo = 1 if prev is not None else 0
+    if int(st.min()) < lo or bool((st + need > bank.numel()).any()):
+        raise ValueError('additive_mix: segment outside the noise bank of {} samples (starts {}, '
+                         'lengths {})'.format(bank.numel(), st.tolist(), need.tolist()))
+    if not bool(torch.isfinite(sn).all()):
+        raise ValueError('additive_mix: snrs must be finite, got {}'.format(sn.tolist()))
+    if prev is not None:
+        _chk(prev, 'prev', 1)
+        if prev.numel() != rows:
+            raise ValueError('additive_mix: prev must hold {} values'.format(rows))
+    # one pinned staging buffer, one asynchronous copy: a pageable copy would hold the host until
+    # everything queued on this stream before it (the loader's 20 MB batch copy) has finished
+    args = torch.empty(2 * rows, dtype=torch.int64).pin_memory()
+    args[:rows] = st
+    args[rows:].view(torch.float64).copy_(sn)
+    args = args.to(clean.device, non_blocking=True)
+    st_d, sn_d = args[:rows], args[rows:].view(torch.float64)
+    noisy = torch.empty_like(clean)
+    prev_out = torch.empty_like(prev) if prev is not None else None
+    info = torch.empty((rows, 2), device=clean.device, dtype=torch.float64)
+    istat = torch.empty((rows, 2), device=clean.device, dtype=torch.int32)
+    check(_lib.load().segan_additive_mix(_ptr(clean), _ptr(lens), _ptr(bank), bank.numel(),
+                                         _ptr(st_d), _ptr(sn_d), _ptr(px.contiguous()), _ptr(prev),
+                                         rows, T, _ptr(noisy), _ptr(prev_out), _ptr(info),
+                                         _ptr(istat), _stream()), 'additive_mix')
+    out = dict(Pn=info[:, 0], sf=info[:, 1], n=istat[:, 0], status=istat[:, 1])
+    if prev is not None:
+        out['prev'] = prev_out
+    return noisy, out
+
+
+def _index_arg(index, B, device, what):
+    if index is None:
+        return None, B
+    idx = torch.as_tensor(index).detach().cpu().reshape(-1)
+    if idx.dtype.is_floating_point or idx.dtype == torch.bool or idx.numel() == 0:
+        raise ValueError('{}: index must hold integers, got {}'.format(what, index))
+    if int(idx.min()) < 0 or int(idx.max()) >= B:
+        raise ValueError('{}: index outside 0 .. {}: {}'.format(what, B - 1, idx.tolist()))
+    return idx.to(torch.int32).pin_memory().to(device, non_blocking=True), idx.numel()
+
+
+def pcm16_wave(pcm, index=None):
+    """The clean rows of the int16 slices pcm [B, 2, T+1] (the layout of `pcm16_prep`) for the
+    batch items `index` (host integers; None: all) as the fp32 min-max-normalised wave [n, T]
+    (se_dataset.py:108-117, no pre-emphasis) and prev [n], the same of the sample preceding each
+    slice."""
+    if not isinstance(pcm, torch.Tensor) or pcm.dtype != torch.int16 or not pcm.is_cuda:
+        raise TypeError('pcm16_wave: pcm must be a CUDA int16 tensor')
+    if pcm.dim() != 3 or pcm.shape[1] != 2 or not pcm.is_contiguous() or pcm.shape[2] < 2:
+        raise ValueError('pcm16_wave: pcm must be contiguous [B, 2, T+1]')
+    B, T = pcm.shape[0], pcm.shape[2] - 1
+    idx, n = _index_arg(index, B, pcm.device, 'pcm16_wave')
+    if n == 0 or n > 65535:
+        raise ValueError('pcm16_wave: 1 .. 65535 rows, got {}'.format(n))
+    wave = torch.empty((n, T), device=pcm.device, dtype=torch.float32)
+    prev = torch.empty(n, device=pcm.device, dtype=torch.float32)
+    check(_lib.load().segan_pcm16_wave(ctypes.c_void_p(pcm.data_ptr()), _ptr(idx), _ptr(wave),
+                                       _ptr(prev), n, B, T, _stream()), 'pcm16_wave')
+    return wave, prev
+
+
+def preemph_rows(x, prev, first, out, coef, index=None):
+    """out[index[k]] = pre-emphasis of x[k] (fp32 CUDA [n, T]; out [B, T]): y[t] = x[t] - coef *
+    x[t-1] in double, rounded once, with x[-1] = prev[k]; y[0] = x[0] where first[index[k]] (uint8
+    CUDA [B]) is set.  Only the indexed rows of `out` are written; returns out."""
+    _chk(x, 'x', 2)
+    _chk(prev, 'prev', 1)
+    _chk(out, 'out', 2)
+    if not isinstance(first, torch.Tensor) or first.dtype != torch.uint8 or not first.is_cuda:
+        raise TypeError('preemph_rows: first must be a CUDA uint8 tensor')
+    B, T = out.shape
+    n = x.shape[0]
+    idx, ni = _index_arg(index, B, x.device, 'preemph_rows')
+    if x.shape[1] != T or prev.numel() != n or first.numel() != B or ni != n or n == 0 or n > 65535:
+        raise ValueError('preemph_rows: x [n, T], prev [n], first [B], out [B, T], index [n] '
+                         '(n = B without index) expected')
+    check(_lib.load().segan_preemph_rows(_ptr(x), _ptr(prev), ctypes.c_void_p(first.data_ptr()),
+                                         _ptr(idx), _ptr(out), n, B, T, float(coef), _stream()),
+          'preemph_rows')
+    return out
+
+
 def rmsprop_step(p, g, sq, lr, alpha, eps):
     check(_lib.load().segan_rmsprop_step(_ptr(p), _ptr(g), _ptr(sq), lr, alpha, eps, p.numel(),
                                          _stream()), 'rmsprop_step')

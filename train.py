@@ -8,7 +8,9 @@ same defaults, same `train.opts` dump) driving the HIP engine in `segan_pytorch_
 
 Additions over the reference: `--synthetic N` trains on N fixed-seed synthetic chunk
 pairs (no dataset needed), `--pcm_shard PREFIX` trains from a pre-sliced int16 shard whose
-batches are normalised / pre-emphasised on the GPU, and under torch.distributed.run every
+batches are normalised / pre-emphasised on the GPU (with `--additive_noises DIR` noise is mixed
+into them on the fly at `--additive_snrs` dB, the reference's Additive), and under
+torch.distributed.run every
 rank trains on its shard of each epoch with RCCL gradient averaging.
 """
 import argparse
@@ -130,7 +132,36 @@ FLAGS = [
     ('--pcm_shard', dict(type=str, default=None,
                          help='prefix of a pre-sliced int16 shard (scripts/make_pcm_shard.py): batches '
                               'are normalised and pre-emphasised on the GPU')),
+    ('--additive_noises', dict(type=str, default=None,
+                               help='with --pcm_shard: directory of noise wavs; the noisy row of '
+                                    'each selected item is replaced by clean + noise mixed on the '
+                                    'GPU at an SNR over the P.56 active speech level (the '
+                                    'reference\'s Additive), and \'_additive\' is appended to its '
+                                    'utterance name')),
+    ('--additive_snrs', dict(type=float, nargs='+', default=[0, 5, 10],
+                             help='SNR levels in dB drawn uniformly per item')),
+    ('--additive_prob', dict(type=float, default=1.0,
+                             help='probability that an item is mixed on the fly')),
 ]
+
+
+def check_additive_flags(opts):
+    """The --additive_* flags go together with --pcm_shard; anything else exits with a message."""
+    noises = getattr(opts, 'additive_noises', None)
+    snrs = list(getattr(opts, 'additive_snrs', [0, 5, 10]))
+    prob = getattr(opts, 'additive_prob', 1.0)
+    if noises is None:
+        if snrs != [0, 5, 10] or prob != 1.0:
+            raise SystemExit('--additive_snrs / --additive_prob need --additive_noises DIR')
+        return False
+    if getattr(opts, 'pcm_shard', None) is None or getattr(opts, 'synthetic', 0) > 0:
+        raise SystemExit('--additive_noises mixes noise into the batches of a pcm16 shard on the '
+                         'GPU: it is valid only together with --pcm_shard PREFIX')
+    if not 0.0 <= prob <= 1.0:
+        raise SystemExit('--additive_prob must lie in 0 .. 1, got {}'.format(prob))
+    if len(snrs) == 0:
+        raise SystemExit('--additive_snrs needs at least one level')
+    return True
 
 
 def build_parser():
@@ -142,6 +173,7 @@ def build_parser():
 
 
 def main(opts):
+    use_additive = check_additive_flags(opts)
     if getattr(opts, 'sync_bn', False):
         os.environ['SEGAN_SYNC_BN'] = '1'
     rank, world, local = sdist.init_from_env()
@@ -202,8 +234,14 @@ def main(opts):
                                      seed=opts.seed, drop_last=True)
     if pcm_loader:
         from segan_pytorch_amd.datasets import PCMShardLoader
+        additive = None
+        if use_additive:
+            from segan_pytorch_amd.augment import Additive
+            additive = Additive(opts.additive_noises, opts.additive_snrs)
         dloader = PCMShardLoader(dset, opts.batch_size, opts.preemph, device, sampler=sampler,
-                                 drop_last=(world > 1), num_workers=max(1, min(2, opts.num_workers)))
+                                 drop_last=(world > 1), num_workers=max(1, min(2, opts.num_workers)),
+                                 additive=additive, additive_prob=opts.additive_prob,
+                                 additive_seed=opts.seed + rank)
     else:
         dloader = DataLoader(dset, batch_size=opts.batch_size, shuffle=(sampler is None),
                              sampler=sampler, num_workers=workers, pin_memory=pin,
