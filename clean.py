@@ -5,6 +5,11 @@ the HIP path.
 
     python clean.py --g_pretrained_ckpt ckpt/weights_EOE_G-Generator-N.ckpt \
         --cfg_file ckpt/train.opts --test_files noisy_dir --synthesis_path out --cuda
+
+Files are taken as 16 kHz whatever their header says, as in the reference, unless --resample is
+given: a file of another rate is then converted to 16 kHz int16 on the GPU first (the reference
+leans on librosa.load(path, 16000) or an offline sox pass), and with --keep_rate the enhanced
+signal is converted back and written at the file's own rate and length.
 """
 import argparse
 import glob
@@ -20,6 +25,8 @@ from scipy.io import wavfile
 
 from segan_pytorch_amd.datasets import normalize_wave_minmax, pre_emphasize
 from segan_pytorch_amd.models import SEGAN, WSEGAN
+from segan_pytorch_amd.ops import RESAMPLE_BETA, RESAMPLE_ZEROS
+from segan_pytorch_amd.resample import TARGET_RATE, resample_wav
 
 
 def build_parser():
@@ -33,10 +40,31 @@ def build_parser():
     p.add_argument('--cuda', action='store_true', default=False)
     p.add_argument('--soundfile', action='store_true', default=False)
     p.add_argument('--cfg_file', type=str, default=None)
+    # additions over the reference: absent from the namespace unless given (argparse.SUPPRESS), so
+    # the default namespace stays the reference's eight flags; read them through resample_opts()
+    p.add_argument('--resample', action='store_true', default=argparse.SUPPRESS,
+                   help='convert files that are not 16 kHz to 16 kHz int16 on the GPU before '
+                        'enhancing them (without it the rate in the header is ignored)')
+    p.add_argument('--keep_rate', action='store_true', default=argparse.SUPPRESS,
+                   help='implies --resample; convert the enhanced signal back to the file\'s rate, '
+                        'trim it to the file\'s length and write it at that rate')
+    p.add_argument('--resample_zeros', type=int, default=argparse.SUPPRESS,
+                   help='zero crossings a side of the conversion filter (default {}; 10 with '
+                        '--resample_beta 5.0 is scipy\'s default)'.format(RESAMPLE_ZEROS))
+    p.add_argument('--resample_beta', type=float, default=argparse.SUPPRESS,
+                   help='Kaiser beta of the conversion filter (default {})'.format(RESAMPLE_BETA))
     return p
 
 
+def resample_opts(opts):
+    """(resample, keep_rate, zeros, beta) of a parsed namespace; keep_rate implies resample."""
+    keep = getattr(opts, 'keep_rate', False)
+    return (getattr(opts, 'resample', False) or keep, keep,
+            getattr(opts, 'resample_zeros', RESAMPLE_ZEROS), getattr(opts, 'resample_beta', RESAMPLE_BETA))
+
+
 def main(opts):
+    resample, keep_rate, rs_zeros, rs_beta = resample_opts(opts)
     if opts.cfg_file is None or opts.test_files is None or opts.g_pretrained_ckpt is None:
         raise SystemExit('--cfg_file, --test_files and --g_pretrained_ckpt are required')
     if not (opts.cuda and torch.cuda.is_available()):
@@ -61,11 +89,19 @@ def main(opts):
     beg_t = timeit.default_timer()
     for t_i, twav in enumerate(twavs, start=1):
         rate, wav = wavfile.read(twav)
+        n_in = wav.shape[0]
+        convert = resample and rate != TARGET_RATE
+        if convert:
+            wav = resample_wav(wav, rate, TARGET_RATE, rs_zeros, rs_beta)
         wav = pre_emphasize(normalize_wave_minmax(wav), args.preemph)
         pwav = torch.as_tensor(wav, dtype=torch.float32).view(1, 1, -1).cuda()
         g_wav, _g_c = segan.generate(pwav, device='cuda')
         out_path = os.path.join(opts.synthesis_path, os.path.basename(twav))
-        wavfile.write(out_path, int(16e3), np.asarray(g_wav, dtype=np.float32))
+        g_wav, out_rate = np.asarray(g_wav, dtype=np.float32), int(16e3)
+        if convert and keep_rate:
+            g_wav = resample_wav(g_wav.reshape(-1), TARGET_RATE, rate, rs_zeros, rs_beta)[:n_in]
+            out_rate = rate
+        wavfile.write(out_path, out_rate, g_wav)
         end_t = timeit.default_timer()
         print('Cleaned {}/{}: {} in {} s'.format(t_i, len(twavs), twav, end_t - beg_t))
         beg_t = timeit.default_timer()

@@ -2,8 +2,11 @@
 the clean wavs of the same names, on the MI355X: the reference's eval_noisy_performance.py.
 
     python eval_noisy_performance.py --test_wavs DIR --clean_wavs DIR --logfile FILE [--stoi]
+                                     [--resample]
 
-16 kHz wavs only (int16 files are scaled by 1/32768, float files used as they are); PESQ needs
+16 kHz wavs only (int16 files are scaled by 1/32768, float files used as they are), unless
+--resample converts files of other rates to 16 kHz on the GPU first (int16 files to int16, float
+files to float32; --resample_zeros / --resample_beta set the filter); PESQ needs
 the external `pesqmain` on PATH (NaN, and so NaN CSIG / CBAK / COVL, without it).  --stoi adds
 a STOI column (quality.stoi on the GPU, both files truncated to their common length) and a final
 mean STOI line."""
@@ -21,10 +24,16 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def read_wav(path):
+def read_wav(path, opts=None):
     from scipy.io import wavfile
     rate, x = wavfile.read(path)
-    if rate != 16000:
+    if rate != 16000 and getattr(opts, 'resample', False):
+        from segan_pytorch_amd.resample import resample_wav
+        try:
+            x = resample_wav(x, rate, 16000, opts.resample_zeros, opts.resample_beta)
+        except (TypeError, ValueError, RuntimeError) as e:
+            raise SystemExit('{}: {}'.format(path, e))
+    elif rate != 16000:
         raise SystemExit('{}: sample rate {} Hz; only 16 kHz wavs are supported (no '
                          'resampling)'.format(path, rate))
     if x.dtype == np.int16:
@@ -51,8 +60,8 @@ def main(opts):
         for n_i, noisy_wav in enumerate(noisy_wavs, start=1):
             bname = os.path.splitext(os.path.basename(noisy_wav))[0]
             clean_wav = os.path.join(opts.clean_wavs, bname + '.wav')
-            noisy = read_wav(noisy_wav)
-            clean = read_wav(clean_wav)
+            noisy = read_wav(noisy_wav, opts)
+            clean = read_wav(clean_wav, opts)
             beg_t = timeit.default_timer()
             r = composite_eval(torch.from_numpy(clean).cuda(), torch.from_numpy(noisy).cuda())
             csig, cbak, covl, pesq, ssnr = (float(r[k][0]) for k in
@@ -81,11 +90,20 @@ def main(opts):
         print('mean STOI: ', np.mean(metrics['stoi']))
 
 
-if __name__ == '__main__':
+def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument('--test_wavs', type=str, required=True)
     parser.add_argument('--clean_wavs', type=str, required=True)
     parser.add_argument('--logfile', type=str, required=True)
     parser.add_argument('--stoi', action='store_true', default=False,
                         help='also compute STOI (short-time objective intelligibility)')
-    main(parser.parse_args())
+    parser.add_argument('--resample', action='store_true', default=False,
+                        help='convert wavs that are not 16 kHz to 16 kHz on the GPU instead of '
+                             'refusing them')
+    from segan_pytorch_amd.resample import add_filter_flags
+    add_filter_flags(parser)
+    return parser
+
+
+if __name__ == '__main__':
+    main(build_parser().parse_args())

@@ -471,6 +471,43 @@ int segan_pcm16_wave(const int16_t* pcm, const int* index, float* wave, float* p
 int segan_preemph_rows(const float* x, const float* prev, const unsigned char* first,
                        const int* index, float* y, int n, int B, int T, double coef, void* stream);
 
+/* ---- sample-rate conversion (the reference's librosa.load(path, 16000), se_dataset.py:72,408, or
+ * an offline sox pass) -----------------------------------------------------
+ * Rows of audio converted by p / q = rate_out / rate_in (lowest terms), fp64 arithmetic.  The
+ * filter is scipy.signal.resample_poly's: mx = max(p, q), lh = zeros*mx, h[t] = sinc(t / mx) *
+ * kaiser(2 lh + 1, beta)[t + lh] for t = -lh .. lh, taps G[t] = p h[t] / sum(h).  Row r holds
+ * Lx = lengths[r] samples (device int[rows], clamped to 0 .. T; NULL: all T) and yields
+ * Ly = ceil(Lx p / q) outputs y[m] = sum_n x[n] G[m q - n p] over |m q - n p| <= lh, 0 <= n < Lx
+ * (ascending n); outputs from Ly to Ly_max are zero.  Equal rates are the identity (p = q = 1, one
+ * tap 1.0).  (zeros, beta) = (10, 5.0) is scipy's default filter and the one STOI uses; the package's
+ * default is (32, 8.6).  sum(h) is taken in index order, as segan_stoi_plan takes it (towards 10 kHz at
+ * (10, 5.0) the taps are then its taps bit for bit), unless that order's rounding moves a tap by more
+ * than 1e-15: then a compensated sum normalises, and the taps stay within 1e-15 of the exact filter.
+ * Limits: rates 4000 .. 192000 Hz, zeros 1 .. 64, beta 0 .. 20, max(p, q) <= 4096, Ly <= 2^30:
+ * outside them -3 (unsupported); -1 for arguments that are no rates, counts, finite non-negative
+ * beta, dtypes or sizes at all.  Both are reported before anything is launched.
+ *   segan_resample_plan (host only, no device): pq[2] = (p, q); *ntaps = 2 lh + 1 taps, written to
+ *     taps when it is not NULL (cap >= *ntaps).
+ *   segan_resample_dims (host only): dims[2] = (Ly for rows of T samples, the kernel's output tile:
+ *     one workgroup computes that many consecutive outputs of one row).
+ *   segan_resample: x [rows][T] of x_dtype (SEGAN_DT_F32, or SEGAN_DT_I16 with the values used as
+ *     they are) -> y [rows][Ly_max] of y_dtype (SEGAN_DT_F64; SEGAN_DT_F32, rounded once from the
+ *     fp64 sum; SEGAN_DT_I16, rounded half to even and saturated to -32768 .. 32767, never
+ *     wrapped).  Ly_max >= the Ly of T.  out_lengths (optional) int[rows] = each row's Ly.  nclip
+ *     (optional) int[rows] = the row's saturated samples (0 unless y is int16); counting them needs
+ *     the workspace ws, int[rows * ceil(Ly_max / tile)] (may be NULL otherwise).  The polyphase
+ *     tap table is built and uploaded on the first call per (device, p, q, zeros, beta) and kept.
+ *     No atomics; a row's result is bitwise independent of the other rows and of its position. */
+#define SEGAN_DT_F32 0
+#define SEGAN_DT_I16 1
+#define SEGAN_DT_F64 2
+int segan_resample_plan(int rate_in, int rate_out, int zeros, double beta, int* pq, int* ntaps,
+                        double* taps, int cap);
+int segan_resample_dims(int T, int rate_in, int rate_out, int* dims);
+int segan_resample(const void* x, int x_dtype, const int* lengths, int rows, int T, int rate_in,
+                   int rate_out, int zeros, double beta, void* y, int y_dtype, int Ly_max,
+                   int* out_lengths, int* nclip, int* ws, void* stream);
+
 /* ---- optimizers (model.py:219-228) ---------------------------------------------------- */
 /* torch.optim.RMSprop (no momentum, not centered): sq = alpha*sq + (1-alpha)*g*g;
  * p -= lr * g / (sqrt(sq) + eps), over a flat arena of n floats. */

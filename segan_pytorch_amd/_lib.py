@@ -101,6 +101,10 @@ SIGNATURES = {
     'segan_stoi': (c_int, [_P, _P, _P, c_int, c_int, c_int] + [_P] * 13),
     'segan_asl_p56': (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     'segan_additive_mix': (c_int, [_P, _P, _P, c_int64, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P]),
+    'segan_resample_plan': (c_int, [c_int, c_int, c_int, c_double, POINTER(c_int), POINTER(c_int), _P, c_int]),
+    'segan_resample_dims': (c_int, [c_int, c_int, c_int, POINTER(c_int)]),
+    'segan_resample': (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_double, _P, c_int,
+                               c_int, _P, _P, _P, _P]),
     'segan_pcm16_wave': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
     'segan_preemph_rows': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_double, _P]),
     'segan_rmsprop_step': (c_int, [_P, _P, _P, c_float, c_float, c_float, c_int64, _P]),

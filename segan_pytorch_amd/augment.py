@@ -15,7 +15,9 @@ class NoiseBank(object):
     copy is made on first use.  `NoiseBank(list_of_arrays)` takes float arrays as they are and
     int16 arrays as int16 / 32768; `NoiseBank.from_dir(dir)` reads every *.wav of a directory
     (16-bit PCM -> int16 / 32768, which is what the reference's `librosa.load(sr=None)` yields;
-    multi-channel files are averaged as librosa does)."""
+    multi-channel files are averaged as librosa does).  The rate in the headers is ignored unless
+    `from_dir(dir, target_rate=16000)` is given: files of another rate are then converted to it on
+    the GPU first (`resample.resample_many`: int16 -> int16, channels averaged before)."""
 
     def __init__(self, arrays, files=None):
         arrays = [self._as_float(a) for a in arrays]
@@ -44,12 +46,19 @@ class NoiseBank(object):
         return np.ascontiguousarray(a.reshape(-1), dtype=np.float32)
 
     @classmethod
-    def from_dir(cls, noises_dir):
+    def from_dir(cls, noises_dir, target_rate=None, resample_zeros=ops.RESAMPLE_ZEROS,
+                 resample_beta=ops.RESAMPLE_BETA):
         from scipy.io import wavfile
         names = sorted(glob.glob(os.path.join(noises_dir, '*.wav')))
         if len(names) == 0:
             raise ValueError('[!] No noises found in {}'.format(noises_dir))
-        return cls([wavfile.read(n)[1] for n in names], files=names)
+        read = [wavfile.read(n) for n in names]
+        wavs = [w for _, w in read]
+        if target_rate is not None:
+            from .resample import resample_many
+            wavs, _ = resample_many(wavs, [r for r, _ in read], target_rate, resample_zeros,
+                                    resample_beta)
+        return cls(wavs, files=names)
 
     def __len__(self):
         return len(self.lengths)
@@ -125,16 +134,18 @@ class Additive(object):
         the reference's arithmetic does;
       * Pn == 0 (a segment of digital silence; inf / NaN in the reference) gives noisy == clean,
         flagged in info['status'] (ops.ADDITIVE_PN0).
-    `do_IRS=True` raises NotImplementedError, as the reference's `apply_IRS` does."""
+    `do_IRS=True` raises NotImplementedError, as the reference's `apply_IRS` does.  `target_rate`
+    (with a directory): noise files of another rate are converted to it on the GPU when they are
+    read (`NoiseBank.from_dir`); without it their rate is ignored."""
 
-    def __init__(self, noises, snr_levels=[0, 5, 10], do_IRS=False, seed=None):
+    def __init__(self, noises, snr_levels=[0, 5, 10], do_IRS=False, seed=None, target_rate=None):
         if do_IRS:
             raise NotImplementedError('Under construction!')
         if isinstance(noises, NoiseBank):
             self.bank = noises
         elif isinstance(noises, (str, os.PathLike)):
             self.noises_dir = noises
-            self.bank = NoiseBank.from_dir(noises)
+            self.bank = NoiseBank.from_dir(noises, target_rate=target_rate)
         else:
             self.bank = NoiseBank(noises)
         if len(snr_levels) == 0:

@@ -143,8 +143,34 @@ class SEDataset(Dataset):
 SHARD_MAGIC = 'segan-pcm16-shard-v1'
 
 
+RESAMPLE_PAIRS = 64      # wav pairs read, converted and sliced together by build_pcm_shard
+
+
+def _read_pairs(clean_names, noisy_names, target_rate, zeros, beta):
+    """(clean path, noisy path, clean wav, noisy wav) of every pair; with `target_rate` the wavs of
+    another rate come converted to it (int16 -> int16), RESAMPLE_PAIRS pairs per batch."""
+    from scipy.io import wavfile
+    if target_rate is None:
+        for cpath, npath in zip(clean_names, noisy_names):
+            yield cpath, npath, wavfile.read(cpath)[1], wavfile.read(npath)[1]
+        return
+    from . import ops
+    from .resample import resample_many
+    zeros = ops.RESAMPLE_ZEROS if zeros is None else zeros
+    beta = ops.RESAMPLE_BETA if beta is None else beta
+    for beg in range(0, len(clean_names), RESAMPLE_PAIRS):
+        paths = list(zip(clean_names[beg:beg + RESAMPLE_PAIRS], noisy_names[beg:beg + RESAMPLE_PAIRS]))
+        read = [wavfile.read(f) for pair in paths for f in pair]
+        for f, (_, w) in zip((f for pair in paths for f in pair), read):
+            if w.dtype != np.int16:
+                raise ValueError('pcm shards hold 16-bit PCM; {} is {}'.format(f, w.dtype))
+        wavs, _ = resample_many([w for _, w in read], [r for r, _ in read], target_rate, zeros, beta)
+        for k, (cpath, npath) in enumerate(paths):
+            yield cpath, npath, wavs[2 * k], wavs[2 * k + 1]
+
+
 def build_pcm_shard(clean_dir, noisy_dir, out_prefix, slice_size=2 ** 14, stride=0.5,
-                    max_samples=None):
+                    max_samples=None, target_rate=None, resample_zeros=None, resample_beta=None):
     """Cut every clean/noisy wav pair into `slice_size` windows (same windows as
     `SEDataset` / se_dataset.py:62-88) and store them as raw int16 PCM:
 
@@ -153,7 +179,12 @@ def build_pcm_shard(clean_dir, noisy_dir, out_prefix, slice_size=2 ** 14, stride
       <out_prefix>.json    {magic, n_items, slice_size, names[], slice_idx[], first[]}
 
     The reference re-reads and re-normalises both full wav files for every item
-    (se_dataset.py:190-198,309-353); at the HIP step's rate that starves the GPU."""
+    (se_dataset.py:190-198,309-353); at the HIP step's rate that starves the GPU.
+
+    The rate in the wav headers is ignored unless `target_rate` (16000) is given: files of another
+    rate are then converted to int16 at that rate on the GPU (`resample.resample_many`, batches of
+    `RESAMPLE_PAIRS` pairs, filter `resample_zeros` / `resample_beta`, default (32, 8.6)) before
+    they are sliced; files already at the target rate are untouched."""
     import glob
     from scipy.io import wavfile
     clean_names = sorted(glob.glob(os.path.join(clean_dir, '*.wav')))
@@ -163,8 +194,8 @@ def build_pcm_shard(clean_dir, noisy_dir, out_prefix, slice_size=2 ** 14, stride
     if max_samples is not None:
         clean_names, noisy_names = clean_names[:max_samples], noisy_names[:max_samples]
     rows, names, sidx, first = [], [], [], []
-    for cpath, npath in zip(clean_names, noisy_names):
-        c, n = wavfile.read(cpath)[1], wavfile.read(npath)[1]
+    for cpath, npath, c, n in _read_pairs(clean_names, noisy_names, target_rate, resample_zeros,
+                                          resample_beta):
         if c.dtype != np.int16 or n.dtype != np.int16:
             raise ValueError('pcm shards hold 16-bit PCM; {} is {}'.format(cpath, c.dtype))
         name = os.path.splitext(os.path.basename(cpath))[0]

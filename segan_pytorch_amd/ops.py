@@ -1269,6 +1269,107 @@ def additive_mix(clean, bank, starts, snrs, px, lengths=None, prev=None):
     return noisy, out
 
 
+RESAMPLE_RATES = (4000, 192000)
+RESAMPLE_ZEROS = 32          # the one default of every layer: flat to 7.5 kHz and at most -89 dB
+RESAMPLE_BETA = 8.6          # beyond 9 kHz for 48 -> 16 kHz.  (10, 5.0) is scipy's default.
+RESAMPLE_ZEROS_MAX = 64
+RESAMPLE_BETA_MAX = 20.0
+_RESAMPLE_DT = {torch.float32: 0, torch.int16: 1, torch.float64: 2}    # SEGAN_DT_*
+
+
+def _resample_args(rate_in, rate_out, zeros, beta):
+    rate_in = _int_arg(rate_in, 'resample: rate_in', *RESAMPLE_RATES)
+    rate_out = _int_arg(rate_out, 'resample: rate_out', *RESAMPLE_RATES)
+    zeros = _int_arg(zeros, 'resample: zeros', 1, RESAMPLE_ZEROS_MAX)
+    try:
+        b = None if isinstance(beta, bool) else float(beta)
+    except (TypeError, ValueError):
+        b = None
+    if b is None or not 0.0 <= b <= RESAMPLE_BETA_MAX:
+        raise ValueError('resample: beta must be a number from 0 to {}, got {!r}'.format(
+            RESAMPLE_BETA_MAX, beta))
+    return rate_in, rate_out, zeros, b
+
+
+def resample_plan(rate_in, rate_out, zeros=RESAMPLE_ZEROS, beta=RESAMPLE_BETA):
+    """The host-side plan of a conversion rate_in -> rate_out (no device involved): (p, q, taps)
+    with p / q = rate_out / rate_in in lowest terms and the fp64 CPU tensor of 2 zeros max(p, q) + 1
+    taps p h / sum(h), h[t] = sinc(t / max(p, q)) kaiser(beta) — scipy.signal.resample_poly's
+    filter; (zeros, beta) = (10, 5.0) is scipy's default.  Equal rates: (1, 1, [1.0])."""
+    rate_in, rate_out, zeros, beta = _resample_args(rate_in, rate_out, zeros, beta)
+    lib = _lib.load()
+    pq, n = (ctypes.c_int * 2)(), ctypes.c_int()
+    check(lib.segan_resample_plan(rate_in, rate_out, zeros, beta, pq, ctypes.byref(n), None, 0),
+          'resample_plan')
+    taps = torch.empty(n.value, dtype=torch.float64)
+    check(lib.segan_resample_plan(rate_in, rate_out, zeros, beta, pq, ctypes.byref(n), _ptr(taps),
+                                  n.value), 'resample_plan')
+    return pq[0], pq[1], taps
+
+
+def resample_dims(T, rate_in, rate_out):
+    """(Ly, tile): the samples T samples at rate_in become at rate_out, ceil(T p / q), and the
+    number of consecutive outputs one workgroup of the kernel computes (host only)."""
+    rate_in, rate_out, _, _ = _resample_args(rate_in, rate_out, 1, 0.0)
+    dims = (ctypes.c_int * 2)()
+    check(_lib.load().segan_resample_dims(_int_arg(T, 'resample: T', 0, 2 ** 31 - 1), rate_in,
+                                          rate_out, dims), 'resample_dims')
+    return dims[0], dims[1]
+
+
+def resample(x, rate_in, rate_out, lengths=None, out_dtype=None, zeros=RESAMPLE_ZEROS,
+             beta=RESAMPLE_BETA):
+    """Sample-rate conversion of each row of x [rows, T] (a CUDA tensor, float32 or int16 with the
+    values used as they are) from rate_in to rate_out Hz on the device, fp64 arithmetic (DESIGN.md
+    section 12): scipy.signal.resample_poly's polyphase filter with a Kaiser window of `zeros`
+    zero crossings a side and `beta` ((10, 5.0) is scipy's default).  Row r is x[r, :lengths[r]]
+    (all T without `lengths`: host integers, or an int32 CUDA tensor that is used as it is and
+    clamped to 0 .. T on the device).  out_dtype: torch.float64, torch.float32 (rounded once from
+    the fp64 sum) or torch.int16 (rounded half to even, saturated); default: x's dtype.
+    Returns (y [rows, ceil(T p / q)], info): row r holds info['lengths'][r] = ceil(len_r p / q)
+    samples and zeros after them; info['nclip'][r] = its saturated samples (int16 output; 0
+    otherwise).  Both are int32 device tensors.  No device-to-host copy."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError('resample: x must be a tensor, got {}'.format(type(x)))
+    if not x.is_cuda:
+        raise RuntimeError('resample: x is on {}: segan_pytorch_amd runs only on an MI355X (HIP) '
+                           'device; there is no CPU path'.format(x.device))
+    if x.dtype not in (torch.float32, torch.int16):
+        raise TypeError('resample: x must be float32 or int16, got {}'.format(x.dtype))
+    out_dtype = x.dtype if out_dtype is None else out_dtype
+    if out_dtype not in _RESAMPLE_DT:
+        raise TypeError('resample: out_dtype must be torch.float64, float32 or int16, got '
+                        '{}'.format(out_dtype))
+    if x.dim() != 2 or x.shape[0] == 0 or x.shape[1] == 0:
+        raise ValueError('resample: x must be [rows, T] and not empty, got {}'.format(tuple(x.shape)))
+    if not x.is_contiguous():
+        raise ValueError('resample: x must be contiguous')
+    rate_in, rate_out, zeros, beta = _resample_args(rate_in, rate_out, zeros, beta)
+    rows, T = x.shape
+    if lengths is None:
+        lens = None
+    elif isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+        if lengths.dtype != torch.int32 or lengths.shape != (rows,) or lengths.device != x.device:
+            raise ValueError('resample: device lengths must be int32 [{}] on {}'.format(rows, x.device))
+        lens = lengths.contiguous()
+    else:
+        lens = _stoi_lengths(lengths, rows, T, x.device)
+    lib = _lib.load()
+    dims = (ctypes.c_int * 2)()
+    check(lib.segan_resample_dims(T, rate_in, rate_out, dims), 'resample')
+    Ly, tile = dims[0], dims[1]
+    y = torch.empty((rows, Ly), device=x.device, dtype=out_dtype)
+    out_lens = torch.empty(rows, device=x.device, dtype=torch.int32)
+    nclip = torch.empty(rows, device=x.device, dtype=torch.int32)
+    ws = None
+    if out_dtype == torch.int16:
+        ws = torch.empty(rows * ((Ly + tile - 1) // tile), device=x.device, dtype=torch.int32)
+    check(lib.segan_resample(_ptr(x), _RESAMPLE_DT[x.dtype], _ptr(lens), rows, T, rate_in, rate_out,
+                             zeros, beta, _ptr(y), _RESAMPLE_DT[out_dtype], Ly, _ptr(out_lens),
+                             _ptr(nclip), _ptr(ws), _stream()), 'resample')
+    return y, dict(lengths=out_lens, nclip=nclip)
+
+
 def _index_arg(index, B, device, what):
     if index is None:
         return None, B

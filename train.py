@@ -142,6 +142,10 @@ FLAGS = [
                              help='SNR levels in dB drawn uniformly per item')),
     ('--additive_prob', dict(type=float, default=1.0,
                              help='probability that an item is mixed on the fly')),
+    ('--additive_resample', dict(action='store_true', default=False,
+                                 help='with --additive_noises: convert noise wavs that are not '
+                                      '16 kHz (the DEMAND noises are 48 kHz) to 16 kHz on the GPU '
+                                      'when they are read; without it their rate is ignored')),
 ]
 
 
@@ -153,6 +157,8 @@ def check_additive_flags(opts):
     if noises is None:
         if snrs != [0, 5, 10] or prob != 1.0:
             raise SystemExit('--additive_snrs / --additive_prob need --additive_noises DIR')
+        if getattr(opts, 'additive_resample', False):
+            raise SystemExit('--additive_resample needs --additive_noises DIR')
         return False
     if getattr(opts, 'pcm_shard', None) is None or getattr(opts, 'synthetic', 0) > 0:
         raise SystemExit('--additive_noises mixes noise into the batches of a pcm16 shard on the '
@@ -237,7 +243,8 @@ def main(opts):
         additive = None
         if use_additive:
             from segan_pytorch_amd.augment import Additive
-            additive = Additive(opts.additive_noises, opts.additive_snrs)
+            additive = Additive(opts.additive_noises, opts.additive_snrs,
+                                target_rate=16000 if opts.additive_resample else None)
         dloader = PCMShardLoader(dset, opts.batch_size, opts.preemph, device, sampler=sampler,
                                  drop_last=(world > 1), num_workers=max(1, min(2, opts.num_workers)),
                                  additive=additive, additive_prob=opts.additive_prob,
