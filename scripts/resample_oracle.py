@@ -25,9 +25,21 @@ def ratio(rate_in, rate_out):
     return rate_out // g, rate_in // g
 
 
+def design(p, q, zeros, beta):
+    """The taps of p / q: mx = max(p, q), lh = zeros mx, h[t] = sinc(t / mx) kaiser(2 lh + 1, beta)[t + lh]
+    for t = -lh .. lh, G[t + lh] = p h[t] / sum(h).  p == q: [1.0]."""
+    if p == q:
+        return np.ones(1)
+    mx = max(p, q)
+    lh = int(zeros) * mx
+    t = np.arange(-lh, lh + 1)
+    h = np.sinc(t / mx) * np.kaiser(2 * lh + 1, beta)
+    return p * h / np.sum(h)
+
+
 def plan(rate_in, rate_out, zeros=ZEROS, beta=BETA):
-    """(p, q, taps): mx = max(p, q), lh = zeros mx, h[t] = sinc(t / mx) kaiser(2 lh + 1, beta)[t + lh]
-    for t = -lh .. lh, taps G[t + lh] = p h[t] / sum(h).  Equal rates: (1, 1, [1.0])."""
+    """(p, q, taps) of a conversion within the public limits: design(p, q, zeros, beta).  Equal
+    rates: (1, 1, [1.0])."""
     for r in (rate_in, rate_out):
         if not RATE_MIN <= int(r) <= RATE_MAX:
             raise ValueError('rate {} outside {} .. {} Hz'.format(r, RATE_MIN, RATE_MAX))
@@ -38,13 +50,7 @@ def plan(rate_in, rate_out, zeros=ZEROS, beta=BETA):
     if max(p, q) > MX_MAX:
         raise ValueError('{} -> {} Hz reduces to {} / {}: max(p, q) above {}'.format(
             rate_in, rate_out, p, q, MX_MAX))
-    if p == q:
-        return 1, 1, np.ones(1)
-    mx = max(p, q)
-    lh = int(zeros) * mx
-    t = np.arange(-lh, lh + 1)
-    h = np.sinc(t / mx) * np.kaiser(2 * lh + 1, beta)
-    return p, q, p * h / np.sum(h)
+    return p, q, design(p, q, zeros, beta)
 
 
 def out_len(L, p, q):

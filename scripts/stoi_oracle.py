@@ -1,7 +1,8 @@
 """fp64 numpy / scipy oracle of STOI, Taal et al.'s short-time objective intelligibility
 (DESIGN.md section 10 states the rules it follows).  It checks the HIP kernels behind ops.stoi:
 scripts/make_golden_stoi.py runs it to write tests/golden/stoi.pt, and tests/test_stoi.py runs it
-again against that fixture.  Importable on its own (numpy, scipy).
+again against that fixture.  Needs numpy, scipy and resample_oracle.py next to it: the
+resampling to 10 kHz is that oracle's, with scipy's default filter (10, 5.0).
 
     import stoi_oracle as S
     d = S.stoi(clean, processed, 16000)          # float, NaN where STOI is undefined
@@ -10,6 +11,8 @@ again against that fixture.  Importable on its own (numpy, scipy).
 import math
 
 import numpy as np
+
+from resample_oracle import design, ratio, resample, out_len as resampled_length  # noqa: F401
 
 FS = 10000          # internal rate
 N = 256             # frame
@@ -41,43 +44,13 @@ def band_edges():
 
 
 def plan(srate):
-    """(p, q, taps) of the resampling srate -> FS: p / q = FS / srate in lowest terms, and the
-    2*Lh+1 taps g[t + Lh] = p * h / sum(h), h[t] = sinc(t / max(p, q)) * kaiser(2 Lh + 1, 5)[t + Lh],
-    Lh = 10 max(p, q).  FS itself needs no resampling: (1, 1, [1.0])."""
+    """(p, q, taps) of the resampling srate -> FS: p / q = FS / srate in lowest terms and
+    resample_oracle.design(p, q, 10, 5.0).  FS itself needs no resampling: (1, 1, [1.0])."""
     srate = int(srate)
     if not SRATE_MIN <= srate <= SRATE_MAX:
         raise ValueError('srate {} outside {} .. {} Hz'.format(srate, SRATE_MIN, SRATE_MAX))
-    if srate == FS:
-        return 1, 1, np.ones(1)
-    g = math.gcd(FS, srate)
-    p, q = FS // g, srate // g
-    Lh = 10 * max(p, q)
-    t = np.arange(-Lh, Lh + 1)
-    h = np.sinc(t / max(p, q)) * np.kaiser(2 * Lh + 1, 5.0)
-    return p, q, p * h / np.sum(h)
-
-
-def resampled_length(L, p, q):
-    return -(-L * p // q)
-
-
-def resample(x, p, q, taps):
-    """y[m] = sum_n x[n] g[m q - n p + Lh] over |m q - n p| <= Lh, 0 <= n < Lx (ascending n),
-    m = 0 .. ceil(Lx p / q) - 1."""
-    x = np.asarray(x, dtype=np.float64)
-    Lx = len(x)
-    Ly = resampled_length(Lx, p, q)
-    Lh = (len(taps) - 1) // 2
-    c = np.arange(Ly, dtype=np.int64) * q
-    n_lo = np.maximum(-((Lh - c) // p), 0)          # ceil((c - Lh) / p), at least 0
-    n_hi = np.minimum((c + Lh) // p, Lx - 1)
-    y = np.zeros(Ly)
-    for j in range(2 * Lh // p + 2):
-        n = n_lo + j
-        ok = n <= n_hi
-        nn = np.where(ok, n, 0)
-        y += np.where(ok, x[nn] * taps[np.where(ok, c - nn * p + Lh, 0)], 0.0)
-    return y
+    p, q = ratio(srate, FS)
+    return p, q, design(p, q, 10, 5.0)
 
 
 def resample_upfirdn(x, p, q, taps):

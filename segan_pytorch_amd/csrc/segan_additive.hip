@@ -7,8 +7,7 @@
 // fixed order that depends only on the row's own data, so a row's result does not depend on the
 // other rows or on its position in the batch.  Products and sums that the reference rounds
 // separately stay separate here (no contraction into fma unless written as fma).
-#include "segan_common.h"
-#include <math.h>
+#include "segan_signal.h"
 
 #pragma clang fp contract(off)
 
@@ -24,22 +23,10 @@
 
 namespace {
 
-__device__ __forceinline__ int ad_row_samples(const int* __restrict__ lengths, int r, int T) {
-  if (!lengths) return T;
-  const int L = lengths[r];
-  return L < 0 ? 0 : (L > T ? T : L);
-}
-
-__device__ __forceinline__ double ad_wave_sum(double v) {   // result in every lane
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // sum over the workgroup in a fixed order (lanes by butterfly, then waves 0..3); every thread
 // gets the result.  `sh` holds AD_WAVES doubles; reusable after the call returns.
 __device__ __forceinline__ double ad_block_sum(double v, double* sh) {
-  v = ad_wave_sum(v);
+  v = segan_wave_sum(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -172,7 +159,7 @@ __global__ __launch_bounds__(AD_THREADS) void asl_p56_kernel(
   __shared__ int wlast[AD_WAVES][AD_NTHR];
   __shared__ int wcnt[AD_WAVES][AD_NTHR];
   const int r = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int L = ad_row_samples(lengths, r, T);
+  const int L = segan_row_samples(lengths, r, T);
   const float* xr = x + (size_t)r * T;
   double* qr = qout ? qout + (size_t)r * T : nullptr;
 
@@ -315,7 +302,7 @@ __global__ __launch_bounds__(AD_THREADS) void additive_mix_kernel(
   __shared__ double wsum[AD_WAVES], wmax[AD_WAVES], wmin[AD_WAVES];
   __shared__ int wnan[AD_WAVES];
   const int r = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int L = ad_row_samples(lengths, r, T);
+  const int L = segan_row_samples(lengths, r, T);
   const float* cr = clean + (size_t)r * T;
   float* out = noisy + (size_t)r * T;
   const long long s0 = starts[r];

@@ -2,7 +2,7 @@
 //   * de-emphasis  x[n] = coef * x[n-1] + y[n]   (segan/datasets/se_dataset.py:119-126, a
 //     per-sample python loop in the reference) as a blocked parallel scan;
 //   * segmental SNR (segan/utils.py:350-395, numpy) for on-device validation.
-#include "segan_common.h"
+#include "segan_signal.h"
 
 // ---------------------------------------------------------------------------------
 // De-emphasis.  One workgroup per row; a row is walked in slabs of 1024 threads x DE_E
@@ -103,12 +103,6 @@ extern "C" int segan_ssnr_frames(int T, int srate) {
   return nf > 0 ? nf : 0;
 }
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void ssnr_frames_kernel(const float* __restrict__ ref,
                                                           const float* __restrict__ deg,
                                                           float* __restrict__ seg, int T,
@@ -126,8 +120,8 @@ __global__ __launch_bounds__(256) void ssnr_frames_kernel(const float* __restric
     es += c * c;
     en += (c - p) * (c - p);
   }
-  es = wave_sum_d(es);
-  en = wave_sum_d(en);
+  es = segan_wave_sum(es);
+  en = segan_wave_sum(en);
   if (lane == 0) {
     double s = 10.0 * log10(es / (en + eps) + eps);
     s = s < -10.0 ? -10.0 : s;
@@ -151,7 +145,7 @@ __global__ __launch_bounds__(1024) void ssnr_overall_kernel(const float* __restr
     b += e * e;
   }
   for (int i = threadIdx.x; i < nframes; i += 1024) m += seg[(size_t)blockIdx.x * nframes + i];
-  a = wave_sum_d(a); b = wave_sum_d(b); m = wave_sum_d(m);
+  a = segan_wave_sum(a); b = segan_wave_sum(b); m = segan_wave_sum(m);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   if (lane == 0) { s0[w] = a; s1[w] = b; s2[w] = m; }
   __syncthreads();

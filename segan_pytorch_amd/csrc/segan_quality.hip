@@ -4,11 +4,7 @@
 // segan_ssnr_frames) and the Hann-like window 0.5*(1 - cos(2*pi*k/(win+1))), k = 1..win, and
 // compute in fp64 like numpy.  The window, the DFT twiddles and the critical-band table are built
 // on the host with the reference's own expressions and uploaded once per (device, srate).
-#include "segan_common.h"
-#include <math.h>
-#include <deque>
-#include <mutex>
-#include <vector>
+#include "segan_signal.h"
 
 #define QW_NCRIT 25
 #define QW_THREADS 256
@@ -22,8 +18,7 @@ struct QualityTables {
   double* crit;     // [QW_NCRIT][nb]: utils.py:472-497 restricted to bins klo .. klo+nb-1
 };
 
-std::mutex g_tables_mu;
-std::deque<QualityTables> g_tables;   // push_back keeps earlier elements in place
+SeganDeviceTables<QualityTables> g_tables;
 
 // utils.py:448-451 / 600-605: window length and hop (the SSNR ones: segan_ssnr_frames)
 void frame_geometry(int srate, int* win, int* skip) {
@@ -35,19 +30,9 @@ int nfft_of(int win) {   // utils.py:455: int(2 ** np.ceil(np.log(2*winlength)/n
   return (int)pow(2.0, ceil(log(2.0 * win) / log(2.0)));
 }
 
-// Returns the tables of (current device, srate), building and uploading them on first use.
-const QualityTables* get_tables(int srate) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) {
-    segan_set_error("quality: hipGetDevice failed");
-    return nullptr;
-  }
-  std::lock_guard<std::mutex> lock(g_tables_mu);
-  for (const QualityTables& t : g_tables)
-    if (t.device == dev && t.srate == srate) return &t;
-
-  QualityTables t{};
-  t.device = dev;
+// Builds the tables of srate on the host and uploads them to the current device.
+bool build_tables(int srate, QualityTables* tp) {
+  QualityTables& t = *tp;
   t.srate = srate;
   frame_geometry(srate, &t.win, &t.skip);
   t.nfft = nfft_of(t.win);
@@ -57,11 +42,6 @@ const QualityTables* get_tables(int srate) {
   for (int k = 0; k < t.win; ++k) {
     const double time = (double)(k + 1) / (double)(t.win + 1);
     window[k] = 0.5 * (1.0 - cos(2.0 * M_PI * time));
-  }
-  std::vector<double2> tw(t.nfft);
-  for (int m = 0; m < t.nfft; ++m) {
-    const double ang = 2.0 * M_PI * (double)m / (double)t.nfft;
-    tw[m] = make_double2(cos(ang), sin(ang));
   }
   // utils.py:463-497: Gaussian critical-band filters, zeroed below the -30 dB point
   static const double cent_freq[QW_NCRIT] = {
@@ -94,7 +74,7 @@ const QualityTables* get_tables(int srate) {
   }
   if (hi <= lo) {
     segan_set_error("quality: no critical band has a non-zero weight at srate %d", srate);
-    return nullptr;
+    return false;
   }
   t.klo = lo;
   t.nb = hi - lo;
@@ -102,28 +82,19 @@ const QualityTables* get_tables(int srate) {
   for (int i = 0; i < QW_NCRIT; ++i)
     for (int b = 0; b < t.nb; ++b) crit[(size_t)i * t.nb + b] = full[(size_t)i * half + lo + b];
 
-  if (hipMalloc(&t.window, window.size() * sizeof(double)) != hipSuccess ||
-      hipMalloc(&t.tw, tw.size() * sizeof(double2)) != hipSuccess ||
-      hipMalloc(&t.crit, crit.size() * sizeof(double)) != hipSuccess ||
-      hipMemcpy(t.window, window.data(), window.size() * sizeof(double), hipMemcpyHostToDevice) !=
-          hipSuccess ||
-      hipMemcpy(t.tw, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(t.crit, crit.data(), crit.size() * sizeof(double), hipMemcpyHostToDevice) !=
-          hipSuccess) {
-    segan_set_error("quality: table upload failed");
-    return nullptr;
-  }
-  g_tables.push_back(t);
-  return &g_tables.back();
+  return segan_upload(&t.window, window, "quality") &&
+         segan_upload(&t.tw, segan_twiddles(t.nfft), "quality") &&
+         segan_upload(&t.crit, crit, "quality");
+}
+
+// Returns the tables of (current device, srate), building and uploading them on first use.
+const QualityTables* get_tables(int srate) {
+  return g_tables.get(
+      "quality", [=](const QualityTables& t) { return t.srate == srate; },
+      [=](QualityTables* t) { return build_tables(srate, t); });
 }
 
 }  // namespace
-
-__device__ __forceinline__ double wave_sum_all(double v) {   // result in every lane
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // the windowed (clean, processed) frame f of row blockIdx.y as fp64 pairs: fr[k] = (c, p)
 __device__ __forceinline__ void load_frame_pair(double2* fr, const float* __restrict__ ref,
@@ -184,7 +155,7 @@ __global__ __launch_bounds__(QW_THREADS) void wss_kernel(
     const double* cw = crit + (size_t)band * nb;
     double e = 0.0;
     for (int b = lane; b < nb; b += 64) e = fma(sig ? spec[b].y : spec[b].x, cw[b], e);
-    e = wave_sum_all(e);
+    e = segan_wave_sum(e);
     // 10*log10(max(E, 1e-10)), NaN propagating like np.max
     if (lane == 0) energy[sig][band] = 10.0 * log10(e < 1e-10 ? 1e-10 : e);
   }
@@ -226,8 +197,8 @@ __global__ __launch_bounds__(QW_THREADS) void wss_kernel(
     num = W * (d * d);
     den = W;
   }
-  num = wave_sum_all(num);
-  den = wave_sum_all(den);
+  num = segan_wave_sum(num);
+  den = segan_wave_sum(den);
   if (lane == 0) dist[(size_t)blockIdx.y * nframes + f] = num / den;
 }
 
@@ -303,8 +274,8 @@ __global__ __launch_bounds__(QW_THREADS) void llr_kernel(
   }
 #pragma unroll
   for (int j = 0; j <= P; ++j) {
-    Rc[j] = wave_sum_all(Rc[j]);
-    Rp[j] = wave_sum_all(Rp[j]);
+    Rc[j] = segan_wave_sum(Rc[j]);
+    Rp[j] = segan_wave_sum(Rp[j]);
   }
   double Ac[P + 1], Ap[P + 1];
   levinson_lpc<P>(Rc, Ac);

@@ -4,8 +4,16 @@
 //   mx = max(p, q), lh = zeros mx, h[t] = sinc(t / mx) kaiser(2 lh + 1, beta)[t + lh], t = -lh..lh,
 //   G[t] = p h[t] / sum(h);   y[m] = sum_n x[n] G[m q - n p] over |m q - n p| <= lh, 0 <= n < Lx,
 // ascending n, m = 0 .. ceil(Lx p / q) - 1.  (zeros, beta) = (10, 5.0) is scipy's default filter
-// and, towards 10 kHz, the one segan_stoi.hip builds (the same bits wherever the index-order sum
-// of h is accurate enough: rs_make_plan).
+// and, towards 10 kHz, STOI's.
+//
+// This file holds the one resampling kernel and the one filter designer of the library.
+// segan_resample and segan_stoi (stage 1, twice: clean and processed) both go through
+// segan_resample_rows; segan_resample_plan and segan_stoi_plan both go through
+// segan_kaiser_sinc_taps.  The designer has two normalisation modes because the two users are
+// pinned to different things: STOI to its oracle's index-order sum of h at every rate from 4 to
+// 48 kHz, the public converter to 1e-15 of the exactly normalised filter, which the index-order
+// sum misses at some ratios (11025 and 37800 -> 10000 Hz among them).  Where it does not, the
+// two modes give the same bits.
 //
 // One workgroup per (row, tile of RS_TILE outputs).  The input span the tile reads is staged in
 // LDS as doubles, RS_CHUNK samples per pass (one pass unless rate_in / rate_out or zeros is
@@ -19,13 +27,9 @@
 // double.  Tables of at most RS_TAPS_LDS doubles (48 -> 16 kHz and 16 -> 48 kHz at zeros = 32:
 // 193 and 195) are copied to LDS per workgroup; larger ones (160 / 441 at zeros = 32: 28 320
 // doubles, 2469 / 3200: 204 927) are read through L2.  Built on the host and uploaded once per
-// (device, p, q, zeros, beta).  No atomics: the saturation count of an int16 row is the sum of
-// per-tile counts (workspace `ws`) taken by a second launch in a fixed order.
-#include "segan_common.h"
-#include <math.h>
-#include <deque>
-#include <mutex>
-#include <vector>
+// (device, p, q, zeros, beta, designer mode).  No atomics: the saturation count of an int16 row
+// is the sum of per-tile counts (workspace `ws`) taken by a second launch in a fixed order.
+#include "segan_signal.h"
 
 #define RS_THREADS 256
 #define RS_TILE 256           // outputs per workgroup, one per thread
@@ -48,30 +52,6 @@
 
 namespace {
 
-struct ResamplePlan {
-  int p, q, lh;
-  std::vector<double> taps;   // [2*lh + 1]
-};
-
-double rs_bessel_i0(double x) {   // sum_k ((x/2)^k / k!)^2
-  const double y = 0.25 * x * x;
-  double term = 1.0, sum = 1.0;
-  for (int k = 1; k < 200 && term > 1e-18 * sum; ++k) {
-    term *= y / ((double)k * (double)k);
-    sum += term;
-  }
-  return sum;
-}
-
-int rs_gcd(int a, int b) {
-  while (b) {
-    const int t = a % b;
-    a = b;
-    b = t;
-  }
-  return a;
-}
-
 // -1 for arguments that are no rates / filter parameters at all, -3 for ones outside the limits
 int rs_check(const char* what, int rate_in, int rate_out, int zeros, double beta, int* p, int* q) {
   SEGAN_REQUIRE(rate_in > 0 && rate_out > 0, "%s: bad rates %d -> %d Hz", what, rate_in, rate_out);
@@ -83,46 +63,102 @@ int rs_check(const char* what, int rate_in, int rate_out, int zeros, double beta
                  RS_RATE_MAX);
   RS_UNSUPPORTED(zeros <= RS_ZEROS_MAX, "%s: zeros=%d above %d", what, zeros, RS_ZEROS_MAX);
   RS_UNSUPPORTED(beta <= RS_BETA_MAX, "%s: beta=%g above %g", what, beta, RS_BETA_MAX);
-  const int g = rs_gcd(rate_in, rate_out);
-  *p = rate_out / g;
-  *q = rate_in / g;
+  segan_reduce_ratio(rate_out, rate_in, p, q);
   RS_UNSUPPORTED(*p <= RS_MX_MAX && *q <= RS_MX_MAX,
                  "%s: %d -> %d Hz reduces to %d / %d, max(p, q) above %d", what, rate_in, rate_out,
                  *p, *q, RS_MX_MAX);
   return SEGAN_OK;
 }
 
-__host__ __device__ inline long long rs_out_len(long long L, int p, int q) {
-  return (L * p + q - 1) / q;
-}
-
 int rs_dims(const char* what, int T, int p, int q, int* Ly) {
   SEGAN_REQUIRE(T >= 0, "%s: bad length T=%d", what, T);
-  const long long L = rs_out_len(T, p, q);
+  const long long L = segan_resampled_len(T, p, q);
   RS_UNSUPPORTED(L <= RS_LY_MAX, "%s: T=%d converts to %lld samples (at most 2^30)", what, T, L);
   *Ly = (int)L;
   return SEGAN_OK;
 }
 
-// numpy's sinc and kaiser expressions; equal rates are the identity.  The taps are held to 1e-15
-// (absolute) of the exactly normalised filter p h / sum(h).  sum(h) is taken in index order, as
-// make_plan of segan_stoi.hip takes it — towards 10 kHz at (10, 5.0) the taps are then STOI's bit
-// for bit — unless that order's rounding error alone moves the largest tap (p / sum(h), at h = 1)
-// by more than RS_TAP_TOL: over thousands of terms it reaches 1e-14 of the sum.  Then the
-// compensated (Neumaier) sum, which is exact to the last bit or two, normalises instead.
+struct ResampleTables {
+  int device, p, q, zeros, lh, K;
+  double beta;
+  bool compensate;
+  double* tab;   // [K][p], visiting order: tab[j p + s] = G[t_hi(s) - j p] (0 below -lh)
+};
+
+SeganDeviceTables<ResampleTables> g_rs_tables;
+
+const ResampleTables* rs_get_tables(int p, int q, int zeros, double beta, bool compensate) {
+  return g_rs_tables.get(
+      "resample",
+      [=](const ResampleTables& t) {
+        return t.p == p && t.q == q && t.zeros == zeros && t.beta == beta &&
+               t.compensate == compensate;
+      },
+      [=](ResampleTables* t) {
+        std::vector<double> taps;
+        segan_kaiser_sinc_taps(p, q, zeros, beta, compensate, &taps);
+        const int lh = ((int)taps.size() - 1) / 2, K = 2 * lh / p + 1;
+        t->p = p;
+        t->q = q;
+        t->zeros = zeros;
+        t->beta = beta;
+        t->compensate = compensate;
+        t->lh = lh;
+        t->K = K;
+        std::vector<double> tab((size_t)K * p);
+        for (int s = 0; s < p; ++s) {
+          const int phi = (int)(((long long)s * q) % p);
+          const int t_hi = phi + p * ((lh - phi) / p);   // the largest t <= lh with t = phi (mod p)
+          for (int j = 0; j < K; ++j) {
+            const int tt = t_hi - j * p;
+            tab[(size_t)j * p + s] = tt >= -lh ? taps[tt + lh] : 0.0;
+          }
+        }
+        return segan_upload(&t->tab, tab, "resample");
+      });
+}
+
+}  // namespace
+
+void segan_reduce_ratio(int num, int den, int* p, int* q) {
+  int a = num, b = den;   // gcd
+  while (b) {
+    const int t = a % b;
+    a = b;
+    b = t;
+  }
+  *p = num / a;
+  *q = den / a;
+}
+
+static double bessel_i0(double x) {   // sum_k ((x/2)^k / k!)^2
+  const double y = 0.25 * x * x;
+  double term = 1.0, sum = 1.0;
+  for (int k = 1; k < 200 && term > 1e-18 * sum; ++k) {
+    term *= y / ((double)k * (double)k);
+    sum += term;
+  }
+  return sum;
+}
+
+// numpy's sinc and kaiser expressions; p == q == 1 is the identity.  sum(h) is taken in index
+// order, as the STOI oracle's np.sum over these few terms comes out and as STOI's fixtures pin
+// it.  With `compensate` the taps are instead held to 1e-15 (absolute) of the exactly normalised
+// filter: where the index order's rounding error alone moves the largest tap (p / sum(h), at
+// h = 1) by more than RS_TAP_TOL — over thousands of terms it reaches 1e-14 of the sum — the
+// compensated (Neumaier) sum, exact to the last bit or two, normalises.  Elsewhere the two modes
+// give the same bits.
 #define RS_TAP_TOL 1.0e-15
 
-void rs_make_plan(int p, int q, int zeros, double beta, ResamplePlan* pl) {
-  pl->p = p;
-  pl->q = q;
+void segan_kaiser_sinc_taps(int p, int q, int zeros, double beta, bool compensate,
+                            std::vector<double>* taps) {
   if (p == 1 && q == 1) {
-    pl->lh = 0;
-    pl->taps.assign(1, 1.0);
+    taps->assign(1, 1.0);
     return;
   }
   const int mx = p > q ? p : q;
   const int lh = zeros * mx, L = 2 * lh + 1;
-  const double alpha = (L - 1) / 2.0, i0b = rs_bessel_i0(beta);
+  const double alpha = (L - 1) / 2.0, i0b = bessel_i0(beta);
   std::vector<double> h(L);
   double sum = 0.0;               // index order
   double ks = 0.0, kc = 0.0;      // Neumaier: ks + kc
@@ -130,74 +166,16 @@ void rs_make_plan(int p, int q, int zeros, double beta, ResamplePlan* pl) {
     const double u = (double)(n - lh) / (double)mx;
     const double y = M_PI * (u == 0.0 ? 1.0e-20 : u);
     const double r = (n - alpha) / alpha;
-    h[n] = sin(y) / y * (rs_bessel_i0(beta * sqrt(1.0 - r * r)) / i0b);
+    h[n] = sin(y) / y * (bessel_i0(beta * sqrt(1.0 - r * r)) / i0b);
     sum += h[n];
     const double t = ks + h[n];
     kc += fabs(ks) >= fabs(h[n]) ? (ks - t) + h[n] : (h[n] - t) + ks;
     ks = t;
   }
   const double exact = ks + kc;
-  if (fabs(p / sum - p / exact) > RS_TAP_TOL) sum = exact;
-  pl->lh = lh;
-  pl->taps.resize(L);
-  for (int n = 0; n < L; ++n) pl->taps[n] = pl->p * h[n] / sum;
-}
-
-struct ResampleTables {
-  int device, p, q, zeros, lh, K;
-  double beta;
-  double* tab;   // [K][p], visiting order: tab[j p + s] = G[t_hi(s) - j p] (0 below -lh)
-};
-
-std::mutex g_rs_mu;
-std::deque<ResampleTables> g_rs_tables;   // push_back keeps earlier elements in place
-
-const ResampleTables* rs_get_tables(int p, int q, int zeros, double beta) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) {
-    segan_set_error("resample: hipGetDevice failed");
-    return nullptr;
-  }
-  std::lock_guard<std::mutex> lock(g_rs_mu);
-  for (const ResampleTables& t : g_rs_tables)
-    if (t.device == dev && t.p == p && t.q == q && t.zeros == zeros && t.beta == beta) return &t;
-
-  ResamplePlan pl;
-  rs_make_plan(p, q, zeros, beta, &pl);
-  ResampleTables t{};
-  t.device = dev;
-  t.p = p;
-  t.q = q;
-  t.zeros = zeros;
-  t.beta = beta;
-  t.lh = pl.lh;
-  t.K = 2 * pl.lh / p + 1;
-  std::vector<double> tab((size_t)t.K * p);
-  for (int s = 0; s < p; ++s) {
-    const int phi = (int)(((long long)s * q) % p);
-    const int t_hi = phi + p * ((pl.lh - phi) / p);   // the largest t <= lh with t = phi (mod p)
-    for (int j = 0; j < t.K; ++j) {
-      const int tt = t_hi - j * p;
-      tab[(size_t)j * p + s] = tt >= -pl.lh ? pl.taps[tt + pl.lh] : 0.0;
-    }
-  }
-  const size_t bytes = tab.size() * sizeof(double);
-  if (hipMalloc(&t.tab, bytes) != hipSuccess ||
-      hipMemcpy(t.tab, tab.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
-    segan_set_error("resample: table upload failed");
-    return nullptr;
-  }
-  g_rs_tables.push_back(t);
-  return &g_rs_tables.back();
-}
-
-}  // namespace
-
-// the row's valid samples: lengths[r] clamped to [0, T] (all T without lengths)
-__device__ __forceinline__ int rs_row_samples(const int* __restrict__ lengths, int r, int T) {
-  if (!lengths) return T;
-  const int L = lengths[r];
-  return L < 0 ? 0 : (L > T ? T : L);
+  if (compensate && fabs(p / sum - p / exact) > RS_TAP_TOL) sum = exact;
+  taps->resize(L);
+  for (int n = 0; n < L; ++n) (*taps)[n] = p * h[n] / sum;
 }
 
 __device__ __forceinline__ void rs_store(double* y, double v, bool* clipped) { *y = v; }
@@ -228,8 +206,8 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(
   __shared__ int wclip[RS_THREADS / 64];
   const int r = blockIdx.y, t = threadIdx.x;
   const int m0 = blockIdx.x * RS_TILE, m = m0 + t;
-  const int Lx = rs_row_samples(lengths, r, T);
-  const int Ly = (int)rs_out_len(Lx, p, q);
+  const int Lx = segan_row_samples(lengths, r, T);
+  const int Ly = (int)segan_resampled_len(Lx, p, q);
   if (blockIdx.x == 0 && t == 0 && out_lengths) out_lengths[r] = Ly;
   const double* tp = tab;
   if (LDS_TAPS) {
@@ -322,6 +300,20 @@ void rs_launch_out(int y_dtype, const void* x, const int* lengths, void* y, int*
 
 }  // namespace
 
+int segan_resample_rows(int p, int q, int zeros, double beta, bool compensate, const void* x,
+                        int x_dtype, const int* lengths, int rows, int T, void* y, int y_dtype,
+                        int Ly_max, int* out_lengths, int* tile_clip, hipStream_t stream) {
+  const ResampleTables* tb = rs_get_tables(p, q, zeros, beta, compensate);
+  if (!tb) return SEGAN_ELAUNCH;
+  if (x_dtype == SEGAN_DT_F32)
+    rs_launch_out<float>(y_dtype, x, lengths, y, out_lengths, tile_clip, rows, T, Ly_max, tb,
+                         stream);
+  else
+    rs_launch_out<int16_t>(y_dtype, x, lengths, y, out_lengths, tile_clip, rows, T, Ly_max, tb,
+                           stream);
+  return SEGAN_OK;
+}
+
 extern "C" int segan_resample_plan(int rate_in, int rate_out, int zeros, double beta, int* pq,
                                    int* ntaps, double* taps, int cap) {
   SEGAN_REQUIRE(pq && ntaps, "resample_plan: NULL pointer");
@@ -332,9 +324,9 @@ extern "C" int segan_resample_plan(int rate_in, int rate_out, int zeros, double 
   *ntaps = (p == 1 && q == 1) ? 1 : 2 * zeros * (p > q ? p : q) + 1;
   if (taps) {
     SEGAN_REQUIRE(cap >= *ntaps, "resample_plan: %d taps do not fit in %d", *ntaps, cap);
-    ResamplePlan pl;
-    rs_make_plan(p, q, zeros, beta, &pl);
-    for (int n = 0; n < *ntaps; ++n) taps[n] = pl.taps[n];
+    std::vector<double> g;
+    segan_kaiser_sinc_taps(p, q, zeros, beta, true, &g);
+    for (int n = 0; n < *ntaps; ++n) taps[n] = g[n];
   }
   return SEGAN_OK;
 }
@@ -367,14 +359,10 @@ extern "C" int segan_resample(const void* x, int x_dtype, const int* lengths, in
   RS_UNSUPPORTED(Ly_max <= RS_LY_MAX, "resample: Ly_max=%d above 2^30", Ly_max);
   const bool count = y_dtype == SEGAN_DT_I16 && nclip;
   SEGAN_REQUIRE(!count || ws, "resample: int16 output with nclip needs the workspace ws");
-  const ResampleTables* tb = rs_get_tables(p, q, zeros, beta);
-  if (!tb) return SEGAN_ELAUNCH;
   hipStream_t st = (hipStream_t)stream;
-  int* tile_clip = count ? ws : nullptr;
-  if (x_dtype == SEGAN_DT_F32)
-    rs_launch_out<float>(y_dtype, x, lengths, y, out_lengths, tile_clip, rows, T, Ly_max, tb, st);
-  else
-    rs_launch_out<int16_t>(y_dtype, x, lengths, y, out_lengths, tile_clip, rows, T, Ly_max, tb, st);
+  if (int e = segan_resample_rows(p, q, zeros, beta, true, x, x_dtype, lengths, rows, T, y, y_dtype,
+                                  Ly_max, out_lengths, count ? ws : nullptr, st))
+    return e;
   if (count)
     hipLaunchKernelGGL(resample_nclip_kernel, dim3(ceil_div(rows, RS_THREADS / 64)),
                        dim3(RS_THREADS), 0, st, ws, nclip, rows, ceil_div(Ly_max, RS_TILE));

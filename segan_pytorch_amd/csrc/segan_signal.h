@@ -1,0 +1,95 @@
+// What the fp64 signal files (audio, quality, STOI, additive, resample) share: each piece here has
+// more than one user.  The Hann windows are NOT here: quality, STOI and SSNR each round theirs
+// the way their own oracle does.
+#pragma once
+#include "segan_common.h"
+#include <math.h>
+#include <deque>
+#include <mutex>
+#include <vector>
+
+// fp64 sum over the wave by a fixed xor butterfly; the result is in every lane
+__device__ __forceinline__ double segan_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// the row's valid samples: lengths[r] clamped to [0, T] (all T without lengths)
+__device__ __forceinline__ int segan_row_samples(const int* __restrict__ lengths, int r, int T) {
+  if (!lengths) return T;
+  const int L = lengths[r];
+  return L < 0 ? 0 : (L > T ? T : L);
+}
+
+// ceil(L p / q): the samples L samples become when resampled by p / q
+__host__ __device__ inline long long segan_resampled_len(long long L, int p, int q) {
+  return (L * p + q - 1) / q;
+}
+
+// (cos, sin)(2 pi m / n), m = 0 .. n - 1
+inline std::vector<double2> segan_twiddles(int n) {
+  std::vector<double2> tw(n);
+  for (int m = 0; m < n; ++m) {
+    const double ang = 2.0 * M_PI * (double)m / (double)n;
+    tw[m] = make_double2(cos(ang), sin(ang));
+  }
+  return tw;
+}
+
+// Host-built tables that live on a device.  E has an `int device`; get() returns the entry of the
+// current device that `match` accepts, or has `build` fill a new one (device already set; false
+// with the error set on failure) under the lock.  Entries are never freed or moved.
+template <typename E>
+struct SeganDeviceTables {
+  std::mutex mu;
+  std::deque<E> entries;   // push_back keeps earlier elements in place
+
+  template <typename Match, typename Build>
+  const E* get(const char* what, Match match, Build build) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) {
+      segan_set_error("%s: hipGetDevice failed", what);
+      return nullptr;
+    }
+    std::lock_guard<std::mutex> lock(mu);
+    for (const E& e : entries)
+      if (e.device == dev && match(e)) return &e;
+    E e{};
+    e.device = dev;
+    if (!build(&e)) return nullptr;
+    entries.push_back(e);
+    return &entries.back();
+  }
+};
+
+template <typename V>
+bool segan_upload(V** dst, const std::vector<V>& src, const char* what) {
+  const size_t bytes = src.size() * sizeof(V);
+  if (hipMalloc(dst, bytes) == hipSuccess &&
+      hipMemcpy(*dst, src.data(), bytes, hipMemcpyHostToDevice) == hipSuccess)
+    return true;
+  segan_set_error("%s: table upload failed", what);
+  return false;
+}
+
+// ---- defined in segan_resample.hip ----
+
+// p / q = num / den in lowest terms
+void segan_reduce_ratio(int num, int den, int* p, int* q);
+
+// The 2 zeros max(p, q) + 1 taps p h / sum(h) of the Kaiser-windowed sinc h (p == q == 1: [1.0]).
+// compensate = false normalises by the index-order sum of h, always; true swaps in a compensated
+// sum where the index order alone would move the largest tap by more than 1e-15.
+void segan_kaiser_sinc_taps(int p, int q, int zeros, double beta, bool compensate,
+                            std::vector<double>* taps);
+
+// The polyphase resampling of rows x [rows][T] (SEGAN_DT_F32 / I16) by p / q into y
+// [rows][Ly_max] (SEGAN_DT_F64 / F32 / I16): table lookup and launch.  The limits are the
+// callers': segan_resample applies the public ones, segan_stoi takes every rate from 4 to 48 kHz
+// (up to p / q = 10000 / 47999).  The kernel indexes its tap table with int, below
+// 2 zeros max(p, q) + p: under 1e6 for either caller.  out_lengths, tile_clip: optional (see
+// resample_kernel).  SEGAN_OK, or SEGAN_ELAUNCH when the table cannot be built.
+int segan_resample_rows(int p, int q, int zeros, double beta, bool compensate, const void* x,
+                        int x_dtype, const int* lengths, int rows, int T, void* y, int y_dtype,
+                        int Ly_max, int* out_lengths, int* tile_clip, hipStream_t stream);

@@ -1,17 +1,19 @@
 // segan_stoi.hip — STOI, Taal et al.'s short-time objective intelligibility, of rows of clean /
 // processed signals, fp64 throughout (DESIGN.md section 10 states the rules; the numpy oracle is
-// scripts/stoi_oracle.py).  Seven stages, each one launch for all rows, the per-row counts
-// (resampled length, frames, kept frames) derived on the device from `lengths` and `count`:
+// scripts/stoi_oracle.py).  Seven stages, each one launch for all rows (stage 1: one per signal),
+// the per-row counts (resampled length, frames, kept frames) derived on the device from `lengths`
+// and `count`:
 //   resample to 10 kHz -> frame energies -> keep mask, kept-frame list, M -> overlap-add
 //   compaction -> third-octave band envelopes -> segment correlations -> per-row mean.
-// Taps, window, twiddles and the band table are built on the host once per (device, srate).
+// Stage 1 is the library's one resampling kernel (segan_resample_rows, segan_resample.hip) with
+// fp64 output, and the taps are the one designer's (segan_kaiser_sinc_taps) at (zeros, beta) =
+// (10, 5.0) in its index-order mode: STOI's taps are pinned to its oracle at every integer rate
+// from 4 to 48 kHz, the public converter's compensated normalisation differs from them at some
+// (11025 and 37800 Hz among them).  Window, twiddles and the band table are built on the host
+// once per (device, srate).
 // Every sum runs in a fixed order that depends only on the row's own data: a row's result does
 // not depend on the other rows, on T or on the launch.
-#include "segan_common.h"
-#include <math.h>
-#include <deque>
-#include <mutex>
-#include <vector>
+#include "segan_signal.h"
 
 #define ST_FS 10000       // internal rate
 #define ST_N 256          // frame
@@ -29,69 +31,18 @@ struct BandTable {
   int lo[ST_J], hi[ST_J];   // DFT bins [lo, hi) of each band
 };
 
-struct StoiPlan {
-  int p, q, lh;
-  std::vector<double> taps;   // [2*lh + 1]
-  BandTable bands;
-};
-
-double bessel_i0(double x) {   // sum_k ((x/2)^k / k!)^2
-  const double y = 0.25 * x * x;
-  double term = 1.0, sum = 1.0;
-  for (int k = 1; k < 200 && term > 1e-18 * sum; ++k) {
-    term *= y / ((double)k * (double)k);
-    sum += term;
-  }
-  return sum;
-}
-
-int gcd_int(int a, int b) {
-  while (b) {
-    const int t = a % b;
-    a = b;
-    b = t;
-  }
-  return a;
-}
-
 bool srate_ok(int srate) { return srate >= ST_SRATE_MIN && srate <= ST_SRATE_MAX; }
 
-void reduced_ratio(int srate, int* p, int* q) {
-  const int g = gcd_int(ST_FS, srate);
-  *p = ST_FS / g;
-  *q = srate / g;
-}
+// The resampling srate -> 10 kHz: p / q = 10000 / srate in lowest terms, the filter of
+// scipy.signal.resample_poly's default (ST_ZEROS, ST_BETA), sum(h) in index order.
+#define ST_ZEROS 10
+#define ST_BETA 5.0
 
-// The resampling filter srate -> 10 kHz and the band table.  p / q = 10000 / srate in lowest
-// terms, lh = 10 max(p, q); g[t + lh] = p h[t] / sum(h), h[t] = sinc(t / max(p, q)) *
-// kaiser(2 lh + 1, 5)[t + lh] (numpy's sinc and kaiser expressions).  10 kHz is the identity.
 // Band i: the nearest bins (first of equals) to 150 * 2^((2i -+ 1)/6) Hz on k * 10000 / 512.
-void make_plan(int srate, StoiPlan* pl) {
-  if (srate == ST_FS) {
-    pl->p = pl->q = 1;
-    pl->lh = 0;
-    pl->taps.assign(1, 1.0);
-  } else {
-    reduced_ratio(srate, &pl->p, &pl->q);
-    const int mx = pl->p > pl->q ? pl->p : pl->q;
-    const int lh = 10 * mx, L = 2 * lh + 1;
-    const double alpha = (L - 1) / 2.0, i0b = bessel_i0(5.0);
-    std::vector<double> h(L);
-    double sum = 0.0;
-    for (int n = 0; n < L; ++n) {
-      const double u = (double)(n - lh) / (double)mx;
-      const double y = M_PI * (u == 0.0 ? 1.0e-20 : u);
-      const double r = (n - alpha) / alpha;
-      h[n] = sin(y) / y * (bessel_i0(5.0 * sqrt(1.0 - r * r)) / i0b);
-      sum += h[n];
-    }
-    pl->lh = lh;
-    pl->taps.resize(L);
-    for (int n = 0; n < L; ++n) pl->taps[n] = pl->p * h[n] / sum;
-  }
+void make_bands(BandTable* bt) {
   for (int i = 0; i < ST_J; ++i) {
     const double f[2] = {150.0 * pow(2.0, (2 * i - 1) / 6.0), 150.0 * pow(2.0, (2 * i + 1) / 6.0)};
-    int* dst[2] = {&pl->bands.lo[i], &pl->bands.hi[i]};
+    int* dst[2] = {&bt->lo[i], &bt->hi[i]};
     for (int e = 0; e < 2; ++e) {
       int best = 0;
       double bd = INFINITY;
@@ -108,62 +59,34 @@ void make_plan(int srate, StoiPlan* pl) {
 }
 
 struct StoiTables {
-  int device, srate, p, q, lh, klo, nb;
+  int device, srate, p, q, klo, nb;
   BandTable bands;
-  double* taps;     // [2*lh + 1]
   double* window;   // [ST_N]
   double2* tw;      // [ST_NFFT]: (cos, sin)(2*pi*m/512)
 };
 
-std::mutex g_tables_mu;
-std::deque<StoiTables> g_tables;   // push_back keeps earlier elements in place
+SeganDeviceTables<StoiTables> g_tables;
 
 const StoiTables* get_tables(int srate) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) {
-    segan_set_error("stoi: hipGetDevice failed");
-    return nullptr;
-  }
-  std::lock_guard<std::mutex> lock(g_tables_mu);
-  for (const StoiTables& t : g_tables)
-    if (t.device == dev && t.srate == srate) return &t;
-
-  StoiPlan pl;
-  make_plan(srate, &pl);
-  StoiTables t{};
-  t.device = dev;
-  t.srate = srate;
-  t.p = pl.p;
-  t.q = pl.q;
-  t.lh = pl.lh;
-  t.bands = pl.bands;
-  t.klo = ST_NFFT;
-  int khi = 0;
-  for (int i = 0; i < ST_J; ++i) {
-    t.klo = pl.bands.lo[i] < t.klo ? pl.bands.lo[i] : t.klo;
-    khi = pl.bands.hi[i] > khi ? pl.bands.hi[i] : khi;
-  }
-  t.nb = khi - t.klo;
-  std::vector<double> window(ST_N);
-  for (int n = 0; n < ST_N; ++n) window[n] = 0.5 * (1.0 - cos(2.0 * M_PI * (n + 1) / (ST_N + 1)));
-  std::vector<double2> tw(ST_NFFT);
-  for (int m = 0; m < ST_NFFT; ++m) {
-    const double ang = 2.0 * M_PI * (double)m / (double)ST_NFFT;
-    tw[m] = make_double2(cos(ang), sin(ang));
-  }
-  const size_t taps_b = pl.taps.size() * sizeof(double);
-  if (hipMalloc(&t.taps, taps_b) != hipSuccess ||
-      hipMalloc(&t.window, ST_N * sizeof(double)) != hipSuccess ||
-      hipMalloc(&t.tw, ST_NFFT * sizeof(double2)) != hipSuccess ||
-      hipMemcpy(t.taps, pl.taps.data(), taps_b, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(t.window, window.data(), ST_N * sizeof(double), hipMemcpyHostToDevice) !=
-          hipSuccess ||
-      hipMemcpy(t.tw, tw.data(), ST_NFFT * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess) {
-    segan_set_error("stoi: table upload failed");
-    return nullptr;
-  }
-  g_tables.push_back(t);
-  return &g_tables.back();
+  return g_tables.get(
+      "stoi", [=](const StoiTables& t) { return t.srate == srate; },
+      [=](StoiTables* t) {
+        t->srate = srate;
+        segan_reduce_ratio(ST_FS, srate, &t->p, &t->q);
+        make_bands(&t->bands);
+        t->klo = ST_NFFT;
+        int khi = 0;
+        for (int i = 0; i < ST_J; ++i) {
+          t->klo = t->bands.lo[i] < t->klo ? t->bands.lo[i] : t->klo;
+          khi = t->bands.hi[i] > khi ? t->bands.hi[i] : khi;
+        }
+        t->nb = khi - t->klo;
+        std::vector<double> window(ST_N);
+        for (int n = 0; n < ST_N; ++n)
+          window[n] = 0.5 * (1.0 - cos(2.0 * M_PI * (n + 1) / (ST_N + 1)));
+        return segan_upload(&t->window, window, "stoi") &&
+               segan_upload(&t->tw, segan_twiddles(ST_NFFT), "stoi");
+      });
 }
 
 struct StoiDims {
@@ -173,18 +96,14 @@ struct StoiDims {
 // frames of ST_N at hop ST_K starting at 0, the last start at most L - N - 1
 __host__ __device__ inline int stoi_frames(int L) { return L > ST_N ? (L - ST_N - 1) / ST_K + 1 : 0; }
 
-__host__ __device__ inline long long resampled_len(long long L, int p, int q) {
-  return (L * p + q - 1) / q;
-}
-
 // upper bounds of every stage's size for rows of at most T samples
 int stoi_dims(const char* what, int T, int srate, StoiDims* d) {
   SEGAN_REQUIRE(srate_ok(srate), "%s: srate %d outside %d .. %d Hz", what, srate, ST_SRATE_MIN,
                 ST_SRATE_MAX);
   SEGAN_REQUIRE(T >= 0, "%s: bad length T=%d", what, T);
-  int p = 1, q = 1;
-  if (srate != ST_FS) reduced_ratio(srate, &p, &q);
-  const long long Ly = resampled_len(T, p, q);
+  int p, q;
+  segan_reduce_ratio(ST_FS, srate, &p, &q);
+  const long long Ly = segan_resampled_len(T, p, q);
   SEGAN_REQUIRE(Ly <= (1ll << 30), "%s: T=%d resamples to %lld samples (at most 2^30)", what, T,
                 Ly);
   d->Ly = (int)Ly;
@@ -197,22 +116,9 @@ int stoi_dims(const char* what, int T, int srate, StoiDims* d) {
 
 }  // namespace
 
-__device__ __forceinline__ double st_wave_sum(double v) {   // result in every lane
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// the row's valid samples: lengths[r] clamped to [0, T] (all T without lengths)
-__device__ __forceinline__ int row_samples(const int* __restrict__ lengths, int r, int T) {
-  if (!lengths) return T;
-  const int L = lengths[r];
-  return L < 0 ? 0 : (L > T ? T : L);
-}
-
 __device__ __forceinline__ int row_resampled(const int* __restrict__ lengths, int r, int T, int p,
                                              int q) {
-  return (int)resampled_len(row_samples(lengths, r, T), p, q);
+  return (int)segan_resampled_len(segan_row_samples(lengths, r, T), p, q);
 }
 
 // kept frames M -> band frames F' (the last kept frame never starts a band frame) -> segments
@@ -222,31 +128,8 @@ __device__ __forceinline__ int segments(int M) {
   return Fb >= ST_SEG ? Fb - ST_SEG + 1 : 0;
 }
 
-// ---------------------------------------------------------------------------------
-// 1. Resample to 10 kHz: one thread per output sample m of row blockIdx.y, signal blockIdx.z;
-// y[m] = sum_n x[n] g[m q - n p + lh] over |m q - n p| <= lh, 0 <= n < Lx, ascending n.  Samples
-// from the row's ceil(Lx p / q) up to Ly_max are zero.
-// ---------------------------------------------------------------------------------
-__global__ __launch_bounds__(ST_THREADS) void stoi_resample_kernel(
-    const float* __restrict__ ref, const float* __restrict__ deg, const int* __restrict__ lengths,
-    double* __restrict__ xr, double* __restrict__ yr, int T, int Ly_max, int p, int q, int lh,
-    const double* __restrict__ taps) {
-  const int r = blockIdx.y;
-  const int m = blockIdx.x * ST_THREADS + threadIdx.x;
-  if (m >= Ly_max) return;
-  const float* x = (blockIdx.z ? deg : ref) + (size_t)r * T;
-  double* y = (blockIdx.z ? yr : xr) + (size_t)r * Ly_max;
-  const int Lx = row_samples(lengths, r, T);
-  double acc = 0.0;
-  if (m < row_resampled(lengths, r, T, p, q)) {
-    const long long c = (long long)m * q;
-    const long long lo = c - lh <= 0 ? 0 : (c - lh + p - 1) / p;
-    long long hi = (c + lh) / p;
-    hi = hi < Lx - 1 ? hi : Lx - 1;
-    for (long long n = lo; n <= hi; ++n) acc = fma((double)x[n], taps[c - n * p + lh], acc);
-  }
-  y[m] = acc;
-}
+// 1. Resample to 10 kHz: segan_resample_rows, once per signal.  Samples from the row's
+// ceil(Lx p / q) up to Ly_max are zero.
 
 // ---------------------------------------------------------------------------------
 // 2. Frame energies of the clean signal, one wave per frame: 20 log10(||x_j w|| / sqrt(N)) dB,
@@ -269,7 +152,7 @@ __global__ __launch_bounds__(ST_THREADS) void stoi_energy_kernel(
       const double v = x[n] * window[n];
       s = fma(v, v, s);
     }
-    s = st_wave_sum(s);
+    s = segan_wave_sum(s);
     e = 20.0 * log10(sqrt(s) / 16.0);   // sqrt(N) = 16
   }
   if (lane == 0) energy[(size_t)r * F_max + j] = e;
@@ -464,7 +347,7 @@ __global__ __launch_bounds__(ST_THREADS) void stoi_mean_kernel(const double* __r
   const double* row = rho + (size_t)r * S_max * ST_J;
   double s = 0.0;
   for (int k = lane; k < n; k += 64) s += row[k];
-  s = st_wave_sum(s);
+  s = segan_wave_sum(s);
   if (lane == 0) d[r] = n > 0 ? s / n : NAN;
 }
 
@@ -473,20 +356,22 @@ extern "C" int segan_stoi_plan(int srate, int* pq, int* ntaps, double* taps, int
   SEGAN_REQUIRE(pq && ntaps, "stoi_plan: NULL pointer");
   SEGAN_REQUIRE(srate_ok(srate), "stoi_plan: srate %d outside %d .. %d Hz", srate, ST_SRATE_MIN,
                 ST_SRATE_MAX);
-  StoiPlan pl;
-  make_plan(srate, &pl);
-  pq[0] = pl.p;
-  pq[1] = pl.q;
-  *ntaps = (int)pl.taps.size();
+  segan_reduce_ratio(ST_FS, srate, &pq[0], &pq[1]);
+  std::vector<double> g;
+  segan_kaiser_sinc_taps(pq[0], pq[1], ST_ZEROS, ST_BETA, false, &g);
+  *ntaps = (int)g.size();
   if (taps) {
     SEGAN_REQUIRE(cap >= *ntaps, "stoi_plan: %d taps do not fit in %d", *ntaps, cap);
-    for (int n = 0; n < *ntaps; ++n) taps[n] = pl.taps[n];
+    for (int n = 0; n < *ntaps; ++n) taps[n] = g[n];
   }
-  if (bands)
+  if (bands) {
+    BandTable bt;
+    make_bands(&bt);
     for (int i = 0; i < ST_J; ++i) {
-      bands[2 * i] = pl.bands.lo[i];
-      bands[2 * i + 1] = pl.bands.hi[i];
+      bands[2 * i] = bt.lo[i];
+      bands[2 * i + 1] = bt.hi[i];
     }
+  }
   return SEGAN_OK;
 }
 
@@ -516,8 +401,13 @@ extern "C" int segan_stoi(const float* ref, const float* deg, const int* lengths
   if (!tb) return SEGAN_ELAUNCH;
   hipStream_t st = (hipStream_t)stream;
   const dim3 blk(ST_THREADS);
-  hipLaunchKernelGGL(stoi_resample_kernel, dim3(ceil_div(dm.Ly, ST_THREADS), rows, 2), blk, 0, st,
-                     ref, deg, lengths, xr, yr, T, dm.Ly, tb->p, tb->q, tb->lh, tb->taps);
+  const float* in[2] = {ref, deg};
+  double* out[2] = {xr, yr};
+  for (int i = 0; i < 2; ++i)
+    if (int e = segan_resample_rows(tb->p, tb->q, ST_ZEROS, ST_BETA, false, in[i], SEGAN_DT_F32,
+                                    lengths, rows, T, out[i], SEGAN_DT_F64, dm.Ly, nullptr,
+                                    nullptr, st))
+      return e;
   if (dm.F > 0)
     hipLaunchKernelGGL(stoi_energy_kernel, dim3(ceil_div(dm.F, ST_THREADS / 64), rows), blk, 0, st,
                        xr, lengths, energy, T, dm.Ly, dm.F, tb->p, tb->q, tb->window);

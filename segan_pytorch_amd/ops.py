@@ -1067,38 +1067,44 @@ STOI_SRATES = (4000, 48000)
 STOI_BANDS = 15
 
 
-def _stoi_srate(srate):
-    srate_in = srate
+def _int_arg(v, what, lo, hi):
     try:
-        srate = None if isinstance(srate, bool) else operator.index(srate)
+        out = None if isinstance(v, bool) else operator.index(v)
     except TypeError:
-        srate = None
-    if srate is None or not STOI_SRATES[0] <= srate <= STOI_SRATES[1]:
-        raise ValueError('stoi: srate must be an integer from {} to {} Hz, got {!r}'.format(
-            STOI_SRATES[0], STOI_SRATES[1], srate_in))
-    return srate
+        out = None
+    if out is None or not lo <= out <= hi:
+        raise ValueError('{} must be an integer from {} to {}, got {!r}'.format(what, lo, hi, v))
+    return out
+
+
+def _fetch_taps(plan, what):
+    """The two calls of a segan_*_plan entry: plan(pq, ntaps, taps, cap) once without a buffer for
+    the count, once with one.  Returns (p, q, fp64 CPU taps)."""
+    pq, n = (ctypes.c_int * 2)(), ctypes.c_int()
+    check(plan(pq, ctypes.byref(n), None, 0), what)
+    taps = torch.empty(n.value, dtype=torch.float64)
+    check(plan(pq, ctypes.byref(n), _ptr(taps), n.value), what)
+    return pq[0], pq[1], taps
 
 
 def stoi_plan(srate):
     """The host-side plan of STOI at `srate` (no device involved): (p, q, taps, bands) with p / q
     = 10000 / srate in lowest terms, the fp64 CPU tensor of 20 max(p, q) + 1 resampling taps and
     the int CPU tensor [15, 2] of each third-octave band's DFT bins [lo, hi)."""
-    srate = _stoi_srate(srate)
+    srate = _int_arg(srate, 'stoi: srate', *STOI_SRATES)
     lib = _lib.load()
-    pq, n, bands = (ctypes.c_int * 2)(), ctypes.c_int(), (ctypes.c_int * (2 * STOI_BANDS))()
-    check(lib.segan_stoi_plan(srate, pq, ctypes.byref(n), None, 0, None), 'stoi_plan')
-    taps = torch.empty(n.value, dtype=torch.float64)
-    check(lib.segan_stoi_plan(srate, pq, ctypes.byref(n), _ptr(taps), n.value, bands), 'stoi_plan')
-    return pq[0], pq[1], taps, torch.tensor(list(bands), dtype=torch.int64).view(STOI_BANDS, 2)
+    bands = (ctypes.c_int * (2 * STOI_BANDS))()
+    p, q, taps = _fetch_taps(lambda *a: lib.segan_stoi_plan(srate, *a, bands), 'stoi_plan')
+    return p, q, taps, torch.tensor(list(bands), dtype=torch.int64).view(STOI_BANDS, 2)
 
 
-def _stoi_lengths(lengths, rows, T, device):
+def _row_lengths(what, lengths, rows, T, device):
     lens = torch.as_tensor(lengths).detach().cpu()
     if lens.dim() != 1 or lens.numel() != rows or lens.dtype.is_floating_point or lens.dtype in (
             torch.bool, torch.complex64, torch.complex128):
-        raise ValueError('stoi: lengths must hold {} integers, got {}'.format(rows, lengths))
+        raise ValueError('{}: lengths must hold {} integers, got {}'.format(what, rows, lengths))
     if rows and (int(lens.min()) < 0 or int(lens.max()) > T):
-        raise ValueError('stoi: lengths must lie in 0 .. {}, got {}'.format(T, lens.tolist()))
+        raise ValueError('{}: lengths must lie in 0 .. {}, got {}'.format(what, T, lens.tolist()))
     return lens.to(dtype=torch.int32).to(device)
 
 
@@ -1115,9 +1121,9 @@ def stoi_stages(ref, deg, srate=16000, lengths=None):
     _chk(deg, 'deg', 2)
     if ref.shape != deg.shape:
         raise ValueError('stoi: shapes differ {} vs {}'.format(tuple(ref.shape), tuple(deg.shape)))
-    srate = _stoi_srate(srate)
+    srate = _int_arg(srate, 'stoi: srate', *STOI_SRATES)
     rows, T = ref.shape
-    lens = None if lengths is None else _stoi_lengths(lengths, rows, T, ref.device)
+    lens = None if lengths is None else _row_lengths('stoi', lengths, rows, T, ref.device)
     lib = _lib.load()
     dims = (ctypes.c_int * 5)()
     check(lib.segan_stoi_dims(T, srate, dims), 'stoi')
@@ -1157,16 +1163,6 @@ ADDITIVE_PN0 = 2
 ADDITIVE_RANGE = 4
 
 
-def _int_arg(v, what, lo, hi):
-    try:
-        out = None if isinstance(v, bool) else operator.index(v)
-    except TypeError:
-        out = None
-    if out is None or not lo <= out <= hi:
-        raise ValueError('{} must be an integer from {} to {}, got {!r}'.format(what, lo, hi, v))
-    return out
-
-
 def asl_p56_stages(x, srate=16000, nbits=16, lengths=None, _want_q=True):
     """ITU-T P.56 method-B active speech level of each row of x [rows, T] (fp32 CUDA tensor), the
     reference's `Additive.asl_P56` (utils.py:180-297) in fp64 on the device.
@@ -1183,7 +1179,7 @@ def asl_p56_stages(x, srate=16000, nbits=16, lengths=None, _want_q=True):
     rows, T = x.shape
     if rows == 0 or T == 0:
         raise ValueError('asl_p56: empty input {}'.format(tuple(x.shape)))
-    lens = None if lengths is None else _stoi_lengths(lengths, rows, T, x.device)
+    lens = None if lengths is None else _row_lengths('asl_p56', lengths, rows, T, x.device)
     level = torch.empty((rows, 4), device=x.device, dtype=torch.float64)
     counts = torch.empty((rows, ASL_THRESHOLDS), device=x.device, dtype=torch.int32)
     status = torch.empty(rows, device=x.device, dtype=torch.int32)
@@ -1236,7 +1232,7 @@ def additive_mix(clean, bank, starts, snrs, px, lengths=None, prev=None):
         raise ValueError('additive_mix: tensors on different devices')
     st = _host_vec(starts, rows, torch.int64, 'starts')
     sn = _host_vec(snrs, rows, torch.float64, 'snrs')
-    lens = None if lengths is None else _stoi_lengths(lengths, rows, T, clean.device)
+    lens = None if lengths is None else _row_lengths('additive_mix', lengths, rows, T, clean.device)
     need = torch.full((rows,), T, dtype=torch.int64) if lens is None else lens.cpu().to(torch.int64)
     lo = 1 if prev is not None else 0
     if int(st.min()) < lo or bool((st + need > bank.numel()).any()):
@@ -1298,13 +1294,8 @@ def resample_plan(rate_in, rate_out, zeros=RESAMPLE_ZEROS, beta=RESAMPLE_BETA):
     filter; (zeros, beta) = (10, 5.0) is scipy's default.  Equal rates: (1, 1, [1.0])."""
     rate_in, rate_out, zeros, beta = _resample_args(rate_in, rate_out, zeros, beta)
     lib = _lib.load()
-    pq, n = (ctypes.c_int * 2)(), ctypes.c_int()
-    check(lib.segan_resample_plan(rate_in, rate_out, zeros, beta, pq, ctypes.byref(n), None, 0),
-          'resample_plan')
-    taps = torch.empty(n.value, dtype=torch.float64)
-    check(lib.segan_resample_plan(rate_in, rate_out, zeros, beta, pq, ctypes.byref(n), _ptr(taps),
-                                  n.value), 'resample_plan')
-    return pq[0], pq[1], taps
+    return _fetch_taps(lambda *a: lib.segan_resample_plan(rate_in, rate_out, zeros, beta, *a),
+                       'resample_plan')
 
 
 def resample_dims(T, rate_in, rate_out):
@@ -1353,7 +1344,7 @@ def resample(x, rate_in, rate_out, lengths=None, out_dtype=None, zeros=RESAMPLE_
             raise ValueError('resample: device lengths must be int32 [{}] on {}'.format(rows, x.device))
         lens = lengths.contiguous()
     else:
-        lens = _stoi_lengths(lengths, rows, T, x.device)
+        lens = _row_lengths('resample', lengths, rows, T, x.device)
     lib = _lib.load()
     dims = (ctypes.c_int * 2)()
     check(lib.segan_resample_dims(T, rate_in, rate_out, dims), 'resample')

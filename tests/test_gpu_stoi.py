@@ -66,6 +66,31 @@ def test_stages_match_the_oracle(sfx, name):
     assert abs(float(st['d'][0]) - want['d']) <= 1e-8
 
 
+# srate -> T with ceil(T p / q) = 257 outputs, one past the kernel's 256-output tile: tap table in
+# LDS with p > q, in LDS with p < q, 9000 doubles read through L2 (p = 200), q = 24, identity
+@pytest.mark.parametrize('srate,T', [(8000, 205), (16000, 410), (22050, 565), (48000, 1229),
+                                     (10000, 257)])
+def test_stage_1_is_bitwise_the_public_resampler_with_scipys_filter(srate, T):
+    """STOI's resampling to 10 kHz runs through the kernel of ops.resample: xr / yr carry the bits
+    of ops.resample(..., 10000, fp64 out, zeros 10, beta 5.0) wherever the two designer modes give
+    the same taps, as they do at these rates.  Rows of length 0, 1 and T with junk past the
+    length: the row start, the row end, the tile edge and the zero fill."""
+    from segan_pytorch_amd import ops
+    g = torch.Generator().manual_seed(srate)
+    ref = torch.randn(3, T, generator=g).cuda()
+    deg = torch.randn(3, T, generator=g).cuda()
+    lens = [0, 1, T]
+    st = ops.stoi_stages(ref, deg, srate, lengths=lens)
+    assert st['dims'][0] == 257
+    for key, x in (('xr', ref), ('yr', deg)):
+        y, info = ops.resample(x, srate, 10000, lens, torch.float64, 10, 5.0)
+        assert y.shape == st[key].shape == (3, 257)
+        one = -(-10000 // srate)   # the samples one sample becomes
+        assert info['lengths'].tolist() == [0, one, 257]
+        assert torch.equal(_bits(st[key].contiguous()), _bits(y)), (srate, key)
+        assert not y[0].any() and not y[1, one:].any() and y[1, :one].all() and y[2].all()
+
+
 def test_every_fixture_case(sfx):
     from segan_pytorch_amd import ops
     for name in sfx['cases']:

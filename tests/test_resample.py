@@ -35,10 +35,12 @@ def test_plan_taps_match_scipy_firwin(case):
     """segan_resample_plan's taps against scipy.signal.firwin(2 lh + 1, 1 / mx, window=('kaiser',
     beta)) p, absolute 1e-15, for every ratio and filter of the fixture.
 
-    firwin normalises by a pairwise sum of h.  The library sums h in index order, as make_plan of
-    segan_stoi.hip does, wherever that order's own rounding moves no tap by more than 1e-15, and
-    takes a compensated sum otherwise: in index order the 8821 to 204801 terms of 44100 <-> 16000
-    and 16000 -> 12345 Hz leave the sum up to 1.1e-14 (relative) off, and the taps with it."""
+    firwin normalises by a pairwise sum of h.  The library has one designer with two
+    normalisation modes.  This, the public one, sums h in index order wherever that order's own
+    rounding moves no tap by more than 1e-15 and takes a compensated sum otherwise: in index order
+    the 8821 to 204801 terms of 44100 <-> 16000 and 16000 -> 12345 Hz leave the sum up to 1.1e-14
+    (relative) off, and the taps with it.  STOI's mode keeps the index-order sum at every rate,
+    because its taps are pinned to its oracle's bits, not to firwin."""
     from scipy.signal import firwin
     from segan_pytorch_amd import ops
     a, b, zeros, beta = case

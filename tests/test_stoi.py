@@ -47,6 +47,25 @@ def test_plan_rejects_rates_outside_4k_to_48k():
     assert ops.stoi_plan(47999)[2].numel() == 2 * 10 * 47999 + 1
 
 
+@pytest.mark.parametrize('srate', [11025, 37800])
+def test_plan_keeps_the_index_order_sum_where_the_public_designer_compensates(srate):
+    """STOI and ops.resample share one filter designer with two normalisation modes.  At these
+    rates the public mode swaps the index-order sum of h for a compensated one, so its taps at
+    (10, 5.0) are not STOI's bits; STOI's must stay the index-order ones its oracle pins.  Equal
+    bits here would mean STOI has picked up the compensated mode.  The two stay within the
+    rounding of a sequential fp64 sum of n terms, (n - 1) 2^-53 of the peak."""
+    import torch
+    from segan_pytorch_amd import ops
+    staps = ops.stoi_plan(srate)[2]
+    taps = ops.resample_plan(srate, 10000, 10, 5.0)[2]
+    assert taps.shape == staps.shape
+    diff = (taps - staps).abs().max().item()
+    print(srate, 'max |stoi taps - public taps| = {:.3e}'.format(diff))
+    assert not torch.equal(staps, taps)
+    n, peak = taps.numel(), taps.max().item()
+    assert diff <= (n - 1) * 2.0 ** -53 * peak
+
+
 def test_oracle_reproduces_the_fixture(sfx):
     assert set(sfx['cases']) >= {'snrm5', 'snr0', 'snr10', 'snr20', 'scaled', 'zero_run', 'short',
                                  'silent', 'sr10k', 'sr8k', 'sr44k', 'odd_len', 'stage16k',
