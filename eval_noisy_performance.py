@@ -2,14 +2,15 @@
 the clean wavs of the same names, on the MI355X: the reference's eval_noisy_performance.py.
 
     python eval_noisy_performance.py --test_wavs DIR --clean_wavs DIR --logfile FILE [--stoi]
-                                     [--resample]
+                                     [--estoi] [--resample]
 
 16 kHz wavs only (int16 files are scaled by 1/32768, float files used as they are), unless
 --resample converts files of other rates to 16 kHz on the GPU first (int16 files to int16, float
 files to float32; --resample_zeros / --resample_beta set the filter); PESQ needs
 the external `pesqmain` on PATH (NaN, and so NaN CSIG / CBAK / COVL, without it).  --stoi adds
 a STOI column (quality.stoi on the GPU, both files truncated to their common length) and a final
-mean STOI line."""
+mean STOI line; --estoi does the same with an ESTOI column (quality.estoi, extended STOI), after
+STOI's when both are given."""
 import argparse
 import glob
 import os
@@ -51,12 +52,15 @@ def main(opts):
     if not torch.cuda.is_available():
         raise SystemExit('segan_pytorch_amd runs only on an MI355X (HIP) device; pass --cuda on a '
                          'GPU machine (there is no CPU fallback)')
-    from segan_pytorch_amd.quality import composite_eval, stoi
+    from segan_pytorch_amd.quality import composite_eval, estoi, stoi
+    extra = [(name, fn) for name, fn, on in (('STOI', stoi, opts.stoi),
+                                             ('ESTOI', estoi, opts.estoi)) if on]
     noisy_wavs = sorted(glob.glob(os.path.join(opts.test_wavs, '*.wav')))
-    metrics = {'csig': [], 'cbak': [], 'covl': [], 'stoi': []}
+    metrics = {'csig': [], 'cbak': [], 'covl': [], 'STOI': [], 'ESTOI': []}
     timings = []
     with open(opts.logfile, 'w') as out_log:
-        out_log.write('FILE CSIG CBAK COVL PESQ SSNR' + (' STOI' if opts.stoi else '') + '\n')
+        out_log.write('FILE CSIG CBAK COVL PESQ SSNR' + ''.join(' ' + name for name, _ in extra) +
+                      '\n')
         for n_i, noisy_wav in enumerate(noisy_wavs, start=1):
             bname = os.path.splitext(os.path.basename(noisy_wav))[0]
             clean_wav = os.path.join(opts.clean_wavs, bname + '.wav')
@@ -66,10 +70,11 @@ def main(opts):
             r = composite_eval(torch.from_numpy(clean).cuda(), torch.from_numpy(noisy).cuda())
             csig, cbak, covl, pesq, ssnr = (float(r[k][0]) for k in
                                             ('csig', 'cbak', 'covl', 'pesq', 'ssnr'))
-            if opts.stoi:
+            if extra:
                 L = min(len(clean), len(noisy))
-                metrics['stoi'].append(float(stoi(torch.from_numpy(clean[:L]).cuda(),
-                                                  torch.from_numpy(noisy[:L]).cuda())[0]))
+                c, d = torch.from_numpy(clean[:L]).cuda(), torch.from_numpy(noisy[:L]).cuda()
+                for name, fn in extra:
+                    metrics[name].append(float(fn(c, d)[0]))
             end_t = timeit.default_timer()
             timings.append(end_t - beg_t)
             metrics['csig'].append(csig)
@@ -77,7 +82,7 @@ def main(opts):
             metrics['covl'].append(covl)
             out_log.write('{} {:.3f} {:.3f} {:.3f} {:.3f} {:.3}'.format(bname + '.wav', csig,
                                                                         cbak, covl, pesq, ssnr) +
-                          (' {:.4f}'.format(metrics['stoi'][-1]) if opts.stoi else '') + '\n')
+                          ''.join(' {:.4f}'.format(metrics[name][-1]) for name, _ in extra) + '\n')
             print('Processed {}/{} wav, CSIG:{:.3f} CBAK:{:.3f} COVL:{:.3f} '
                   'PESQ:{:.3f} SSNR:{:.3f} '
                   'total time: {:.2f} seconds, mproc: {:.2f}'
@@ -86,8 +91,8 @@ def main(opts):
     print('mean Csig: ', np.mean(metrics['csig']))
     print('mean Cbak: ', np.mean(metrics['cbak']))
     print('mean Covl: ', np.mean(metrics['covl']))
-    if opts.stoi:
-        print('mean STOI: ', np.mean(metrics['stoi']))
+    for name, _ in extra:
+        print('mean {}: '.format(name), np.mean(metrics[name]))
 
 
 def build_parser():
@@ -97,6 +102,9 @@ def build_parser():
     parser.add_argument('--logfile', type=str, required=True)
     parser.add_argument('--stoi', action='store_true', default=False,
                         help='also compute STOI (short-time objective intelligibility)')
+    parser.add_argument('--estoi', action='store_true', default=False,
+                        help='also compute ESTOI (extended STOI, the measure for modulated '
+                             'noise such as babble)')
     parser.add_argument('--resample', action='store_true', default=False,
                         help='convert wavs that are not 16 kHz to 16 kHz on the GPU instead of '
                              'refusing them')

@@ -429,6 +429,17 @@ int segan_stoi_dims(int T, int srate, int* dims);
 int segan_stoi(const float* ref, const float* deg, const int* lengths, int rows, int T, int srate,
                double* xr, double* yr, double* energy, int* mask, int* kept, int* count,
                double* xs, double* ys, double* X, double* Y, double* rho, double* d, void* stream);
+/* ESTOI, extended STOI (Jensen & Taal 2016; DESIGN.md section 10, "ESTOI"): segan_stoi's
+ * arguments, conventions and stages up to the band envelopes X, Y (buffer sizes from
+ * segan_stoi_dims), then per segment s the 15 x 30 windows of X and of Y normalised along their
+ * rows and then their columns (mean removed, unit norm; a vector of no energy, or whose centred
+ * energy is at most 2^-40 of its energy, becomes zeros) and dm[rows][S] = their inner product /
+ * 30 (first max(M-30, 0) segments valid), d[rows] = the mean of the row's dm, NaN without
+ * segments.  No clipping, no energy scaling.  Added without a change of SEGAN_ABI_VERSION: the
+ * export is purely additive, every earlier entry keeps its signature and its results. */
+int segan_estoi(const float* ref, const float* deg, const int* lengths, int rows, int T, int srate,
+                double* xr, double* yr, double* energy, int* mask, int* kept, int* count,
+                double* xs, double* ys, double* X, double* Y, double* dm, double* d, void* stream);
 
 /* ---- on-the-fly additive noise (the reference's Additive, utils.py:43-297)
  * fp64 arithmetic on fp32 rows x / clean [rows][T], row r restricted to its first lengths[r]

@@ -4,6 +4,7 @@ device synchronise: one call per utterance (as eval_noisy_performance.py --stoi 
 batched call over the set padded to its longest utterance with `lengths`.  Prints one JSON line.
 
     python scripts/bench_stoi.py                 # MI355X
+    python scripts/bench_stoi.py --estoi         # and quality.estoi next to it, under 'estoi'
     python scripts/bench_stoi.py --cpu-oracle N  # the fp64 numpy oracle (scripts/stoi_oracle.py)
                                                  # on N of the same utterances, on the CPU
 """
@@ -39,6 +40,8 @@ def main():
     ap.add_argument('--cpu-oracle', type=int, default=0)
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--batch-reps', type=int, default=5)
+    ap.add_argument('--estoi', action='store_true',
+                    help='time quality.estoi the same two ways after STOI, in the same run')
     args = ap.parse_args()
     utts = utterances()
     audio_s = float(np.sum([len(c) for c, _ in utts])) / 16000
@@ -55,17 +58,8 @@ def main():
                                                          utts[:args.cpu_oracle]])) / 16000}))
         return
     import torch
-    from segan_pytorch_amd.quality import stoi
+    from segan_pytorch_amd import quality
     dev = [(torch.from_numpy(c).cuda(), torch.from_numpy(d).cuda()) for c, d in utts]
-    for c, d in dev[:args.warmup]:
-        stoi(c, d)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    per = [stoi(c, d) for c, d in dev]
-    torch.cuda.synchronize()
-    dt_single = time.perf_counter() - t0
-    per = torch.cat(per)
-
     T = max(len(c) for c, _ in utts)
     ref = torch.zeros(len(utts), T)
     deg = torch.zeros(len(utts), T)
@@ -74,20 +68,40 @@ def main():
         deg[i, :len(d)] = torch.from_numpy(d)
     ref, deg = ref.cuda(), deg.cuda()
     lengths = [len(c) for c, _ in utts]
-    stoi(ref, deg, lengths=lengths)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.batch_reps):
-        batched = stoi(ref, deg, lengths=lengths)
-    torch.cuda.synchronize()
-    dt_batch = (time.perf_counter() - t0) / args.batch_reps
-    same = bool(torch.equal(batched.cpu().view(torch.int64), per.cpu().view(torch.int64)))
-    print(json.dumps({'leg': 'mi355x', 'utts': len(utts), 'audio_s': audio_s,
-                      'per_utt_seconds': dt_single, 'per_utt_utts_per_s': len(utts) / dt_single,
-                      'batched_seconds': dt_batch, 'batched_utts_per_s': len(utts) / dt_batch,
-                      'batched_equals_per_utt_bitwise': same,
-                      'nan_rows': int(torch.isnan(per).sum()),
-                      'mean_stoi': float(per[~torch.isnan(per)].mean())}))
+
+    def measure(fn):
+        for c, d in dev[:args.warmup]:
+            fn(c, d)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        per = [fn(c, d) for c, d in dev]
+        torch.cuda.synchronize()
+        dt_single = time.perf_counter() - t0
+        per = torch.cat(per)
+        fn(ref, deg, lengths=lengths)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.batch_reps):
+            batched = fn(ref, deg, lengths=lengths)
+        torch.cuda.synchronize()
+        dt_batch = (time.perf_counter() - t0) / args.batch_reps
+        same = bool(torch.equal(batched.cpu().view(torch.int64), per.cpu().view(torch.int64)))
+        return {'per_utt_seconds': dt_single, 'per_utt_utts_per_s': len(utts) / dt_single,
+                'batched_seconds': dt_batch, 'batched_utts_per_s': len(utts) / dt_batch,
+                'batched_equals_per_utt_bitwise': same,
+                'nan_rows': int(torch.isnan(per).sum()),
+                'mean': float(per[~torch.isnan(per)].mean())}
+
+    out = {'leg': 'mi355x', 'utts': len(utts), 'audio_s': audio_s}
+    r = measure(quality.stoi)
+    out['mean_stoi'] = r.pop('mean')
+    out.update(r)
+    if args.estoi:
+        r = measure(quality.estoi)
+        r['mean_estoi'] = r.pop('mean')
+        r['batched_seconds_over_stois'] = r['batched_seconds'] / out['batched_seconds']
+        out['estoi'] = r
+    print(json.dumps(out))
 
 
 if __name__ == '__main__':

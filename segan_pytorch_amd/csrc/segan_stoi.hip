@@ -13,6 +13,9 @@
 // once per (device, srate).
 // Every sum runs in a fixed order that depends only on the row's own data: a row's result does
 // not depend on the other rows, on T or on the launch.
+// ESTOI (Jensen & Taal 2016; segan_estoi, oracle scripts/estoi_oracle.py) shares stages 1-5
+// (stoi_front) and replaces the last two: each 15 x 30 window of X and of Y is normalised along
+// its rows and then along its columns, d_s is their inner product / 30, d the mean of d_s.
 #include "segan_signal.h"
 
 #define ST_FS 10000       // internal rate
@@ -333,9 +336,11 @@ __global__ __launch_bounds__(ST_THREADS) void stoi_segment_kernel(
 }
 
 // ---------------------------------------------------------------------------------
-// 7. d = mean of the row's S*15 correlations, one wave per row: lane l sums entries l, l+64, ...
-// in order, then a fixed butterfly.  NaN without segments (M = 0 or fewer than 30 band frames).
+// 7. d = mean of the row's S*PER values (STOI: PER = 15 correlations per segment; ESTOI: PER = 1),
+// one wave per row: lane l sums entries l, l+64, ... in order, then a fixed butterfly.  NaN
+// without segments (M = 0 or fewer than 30 band frames).
 // ---------------------------------------------------------------------------------
+template <int PER>
 __global__ __launch_bounds__(ST_THREADS) void stoi_mean_kernel(const double* __restrict__ rho,
                                                                const int* __restrict__ count,
                                                                double* __restrict__ d, int rows,
@@ -343,12 +348,79 @@ __global__ __launch_bounds__(ST_THREADS) void stoi_mean_kernel(const double* __r
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * (ST_THREADS / 64) + (threadIdx.x >> 6);
   if (r >= rows) return;   // whole waves leave
-  const int n = segments(count[r]) * ST_J;
-  const double* row = rho + (size_t)r * S_max * ST_J;
+  const int n = segments(count[r]) * PER;
+  const double* row = rho + (size_t)r * S_max * PER;
   double s = 0.0;
   for (int k = lane; k < n; k += 64) s += row[k];
   s = segan_wave_sum(s);
   if (lane == 0) d[r] = n > 0 ? s / n : NAN;
+}
+
+// ---------------------------------------------------------------------------------
+// ESTOI 6. One wave per (segment s, row): the windows X[:, s:s+30], Y[:, s:s+30] staged in LDS
+// (2 x 450 doubles per wave), then the zero rule along the rows (one lane per (band, signal),
+// the 30 frames in ascending order) and along the columns of the result (one lane per (frame,
+// signal), the 15 bands in ascending order), each lane rewriting its own vector in place:
+//   raw = sum v^2, c = v - mean v, e = sum c^2;  v <- c / sqrt(e) if raw > 0 and e > 2^-40 raw,
+//   else zeros (a degenerate vector correlates with nothing; the relative threshold keeps
+//   rounding residue, 1e-32 of raw where a window's rows are all the same vector, from being
+//   normalised to unit length).
+// d_s = sum Xn Yn / 30: lane l sums entries l, l+64, ... in order, then the fixed butterfly.
+// The four waves of a workgroup work on their own segments; waves without a segment only keep
+// the barriers company.  dm: [rows][S_max].
+// ---------------------------------------------------------------------------------
+#define ES_WIN (ST_J * ST_SEG)
+#define ES_ZERO_RULE 0x1p-40
+
+// the zero rule on the n values v[0], v[stride], ...
+__device__ __forceinline__ void estoi_normalise(double* v, int n, int stride) {
+  double raw = 0.0, sum = 0.0;
+  for (int k = 0; k < n; ++k) {
+    const double a = v[k * stride];
+    raw = fma(a, a, raw);
+    sum += a;
+  }
+  const double mean = sum / n;
+  double e = 0.0;
+  for (int k = 0; k < n; ++k) {
+    const double c = v[k * stride] - mean;
+    e = fma(c, c, e);
+  }
+  const bool keep = raw > 0.0 && e > ES_ZERO_RULE * raw;
+  const double norm = sqrt(e);
+  for (int k = 0; k < n; ++k) v[k * stride] = keep ? (v[k * stride] - mean) / norm : 0.0;
+}
+
+__global__ __launch_bounds__(ST_THREADS) void estoi_segment_kernel(
+    const double* __restrict__ X, const double* __restrict__ Y, const int* __restrict__ count,
+    double* __restrict__ dm, int Fb_max, int S_max) {
+  __shared__ double win[ST_THREADS / 64][2][ES_WIN];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int s = blockIdx.x * (ST_THREADS / 64) + wave;
+  const int r = blockIdx.y;
+  const bool active = s < S_max && s < segments(count[r]);   // wave-uniform
+  double* wx = win[wave][0];
+  double* wy = win[wave][1];
+  if (active) {
+    const size_t base = (size_t)r * ST_J * Fb_max + s;   // frames s .. s+29 < the row's F'
+    for (int k = lane; k < ES_WIN; k += 64) {
+      const int i = k / ST_SEG, f = k - i * ST_SEG;
+      wx[k] = X[base + (size_t)i * Fb_max + f];
+      wy[k] = Y[base + (size_t)i * Fb_max + f];
+    }
+  }
+  __syncthreads();
+  if (active && lane < 2 * ST_J)
+    estoi_normalise((lane < ST_J ? wx : wy) + (lane % ST_J) * ST_SEG, ST_SEG, 1);
+  __syncthreads();
+  if (active && lane < 2 * ST_SEG)
+    estoi_normalise((lane < ST_SEG ? wx : wy) + lane % ST_SEG, ST_J, ST_SEG);
+  __syncthreads();
+  if (!active) return;   // whole waves leave, no barrier follows
+  double acc = 0.0;
+  for (int k = lane; k < ES_WIN; k += 64) acc = fma(wx[k], wy[k], acc);
+  acc = segan_wave_sum(acc);
+  if (lane == 0) dm[(size_t)r * S_max + s] = acc / ST_SEG;
 }
 
 extern "C" int segan_stoi_plan(int srate, int* pq, int* ntaps, double* taps, int cap,
@@ -387,19 +459,21 @@ extern "C" int segan_stoi_dims(int T, int srate, int* dims) {
   return SEGAN_OK;
 }
 
-extern "C" int segan_stoi(const float* ref, const float* deg, const int* lengths, int rows, int T,
-                          int srate, double* xr, double* yr, double* energy, int* mask, int* kept,
-                          int* count, double* xs, double* ys, double* X, double* Y, double* rho,
-                          double* d, void* stream) {
+// Stages 1-5 of both measures: argument checks, then resample -> frame energies -> select ->
+// compaction -> band envelopes on `st`.  `last`, `d`: the caller's last-stage buffers, checked
+// here so that every check precedes the first launch.  dims: the stage sizes for T.
+static int stoi_front(const char* what, const float* ref, const float* deg, const int* lengths,
+                      int rows, int T, int srate, double* xr, double* yr, double* energy,
+                      int* mask, int* kept, int* count, double* xs, double* ys, double* X,
+                      double* Y, const void* last, const void* d, StoiDims* dims, hipStream_t st) {
   SEGAN_REQUIRE(ref && deg && xr && yr && energy && mask && kept && count && xs && ys && X && Y &&
-                    rho && d,
-                "stoi: NULL pointer");
-  SEGAN_REQUIRE(rows > 0 && rows <= 65535 && T > 0, "stoi: bad sizes rows=%d T=%d", rows, T);
-  StoiDims dm;
-  if (int e = stoi_dims("stoi", T, srate, &dm)) return e;
+                    last && d,
+                "%s: NULL pointer", what);
+  SEGAN_REQUIRE(rows > 0 && rows <= 65535 && T > 0, "%s: bad sizes rows=%d T=%d", what, rows, T);
+  StoiDims& dm = *dims;
+  if (int e = stoi_dims(what, T, srate, &dm)) return e;
   const StoiTables* tb = get_tables(srate);
   if (!tb) return SEGAN_ELAUNCH;
-  hipStream_t st = (hipStream_t)stream;
   const dim3 blk(ST_THREADS);
   const float* in[2] = {ref, deg};
   double* out[2] = {xr, yr};
@@ -419,10 +493,41 @@ extern "C" int segan_stoi(const float* ref, const float* deg, const int* lengths
   if (dm.Fb > 0)
     hipLaunchKernelGGL(stoi_band_kernel, dim3(dm.Fb, rows), blk, 0, st, xs, ys, count, X, Y, dm.Lc,
                        dm.Fb, tb->klo, tb->nb, tb->bands, tb->window, tb->tw);
+  return SEGAN_OK;
+}
+
+extern "C" int segan_stoi(const float* ref, const float* deg, const int* lengths, int rows, int T,
+                          int srate, double* xr, double* yr, double* energy, int* mask, int* kept,
+                          int* count, double* xs, double* ys, double* X, double* Y, double* rho,
+                          double* d, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  StoiDims dm;
+  if (int e = stoi_front("stoi", ref, deg, lengths, rows, T, srate, xr, yr, energy, mask, kept,
+                         count, xs, ys, X, Y, rho, d, &dm, st))
+    return e;
+  const dim3 blk(ST_THREADS);
   if (dm.S > 0)
     hipLaunchKernelGGL(stoi_segment_kernel, dim3(ceil_div(dm.S * ST_J, ST_THREADS), rows), blk, 0,
                        st, X, Y, count, rho, dm.Fb, dm.S, pow(10.0, 15.0 / 20.0));
-  hipLaunchKernelGGL(stoi_mean_kernel, dim3(ceil_div(rows, ST_THREADS / 64)), blk, 0, st, rho,
+  hipLaunchKernelGGL(stoi_mean_kernel<ST_J>, dim3(ceil_div(rows, ST_THREADS / 64)), blk, 0, st, rho,
                      count, d, rows, dm.S);
   return segan_check_launch("stoi");
+}
+
+extern "C" int segan_estoi(const float* ref, const float* deg, const int* lengths, int rows, int T,
+                           int srate, double* xr, double* yr, double* energy, int* mask, int* kept,
+                           int* count, double* xs, double* ys, double* X, double* Y, double* dseg,
+                           double* d, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  StoiDims dm;
+  if (int e = stoi_front("estoi", ref, deg, lengths, rows, T, srate, xr, yr, energy, mask, kept,
+                         count, xs, ys, X, Y, dseg, d, &dm, st))
+    return e;
+  const dim3 blk(ST_THREADS);
+  if (dm.S > 0)
+    hipLaunchKernelGGL(estoi_segment_kernel, dim3(ceil_div(dm.S, ST_THREADS / 64), rows), blk, 0,
+                       st, X, Y, count, dseg, dm.Fb, dm.S);
+  hipLaunchKernelGGL(stoi_mean_kernel<1>, dim3(ceil_div(rows, ST_THREADS / 64)), blk, 0, st, dseg,
+                     count, d, rows, dm.S);
+  return segan_check_launch("estoi");
 }

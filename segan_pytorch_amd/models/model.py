@@ -421,15 +421,17 @@ class SEGAN(Model):
         of the enhanced — and with `do_noisy` of the noisy — signal against the clean one.  PESQ
         comes from the external `pesqmain` binary (run in `opts.eval_workers` threads, at most
         16); without it on PATH pesq / csig / cbak / covl are NaN.  With `opts.eval_stoi` set (train.py
-        --eval_stoi) a key 'stoi' (quality.stoi, 16 kHz) is added, computed on the same signals.
+        --eval_stoi) a key 'stoi' (quality.stoi, 16 kHz) is added, computed on the same signals;
+        with `opts.eval_estoi` (train.py --eval_estoi) a key 'estoi' (quality.estoi) likewise.
         De-emphasis runs along time (the reference applies it along axis 0 of the [B, T] batch,
         model.py:474-477)."""
         from .. import ops, quality
         self.G.eval()
         self.D.eval()
         with_stoi = bool(getattr(opts, 'eval_stoi', False))
+        with_estoi = bool(getattr(opts, 'eval_estoi', False))
         keys = ('ssnr', 'snr', 'pesq', 'csig', 'cbak', 'covl', 'wss', 'llr') + (
-            ('stoi',) if with_stoi else ())
+            ('stoi',) if with_stoi else ()) + (('estoi',) if with_estoi else ())
         evals = {k: [] for k in keys}
         noisy_evals = {k: [] for k in keys}
         workers = getattr(opts, 'eval_workers', 2)
@@ -452,6 +454,8 @@ class SEGAN(Model):
                         dst[k] += comp[k].cpu().tolist()
                     if with_stoi:
                         dst['stoi'] += quality.stoi(c, d).cpu().tolist()
+                    if with_estoi:
+                        dst['estoi'] += quality.estoi(c, d).cpu().tolist()
                 if bidx >= max_samples:
                     break
         self.G.train()

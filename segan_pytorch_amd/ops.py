@@ -1108,15 +1108,9 @@ def _row_lengths(what, lengths, rows, T, device):
     return lens.to(dtype=torch.int32).to(device)
 
 
-def stoi_stages(ref, deg, srate=16000, lengths=None):
-    """STOI (Taal et al.'s short-time objective intelligibility, DESIGN.md section 10) of each
-    row of ref / deg [rows, T] with every intermediate, fp64, on the device.  Row r is the signal
-    ref[r, :lengths[r]] (all T without `lengths`; host integers, a CUDA tensor is copied to the
-    host to be checked).  Returns a dict of device tensors, sized for T, of which each row uses
-    its own leading part: xr, yr [rows, Ly] (resampled to 10 kHz), energy, mask, kept
-    [rows, F] (clean frame energies in dB, keep mask, kept frame indices), count [rows] (M),
-    xs, ys [rows, Lc] (compacted), X, Y [rows, 15, Fb] (band envelopes), rho [rows, S, 15]
-    (segment correlations), d [rows]; and dims = (Ly, F, Lc, Fb, S)."""
+def _stoi_run(entry, last, per, ref, deg, srate, lengths):
+    """The argument checks, stage buffers and call that segan_stoi and segan_estoi share: `entry`
+    names the C entry, `last` its last-stage buffer ([rows, S, per], [rows, S] with per = 1)."""
     _chk(ref, 'ref', 2)
     _chk(deg, 'deg', 2)
     if ref.shape != deg.shape:
@@ -1137,16 +1131,29 @@ def stoi_stages(ref, deg, srate=16000, lengths=None):
     count = torch.empty(rows, **i32)
     xs = torch.empty((2, rows, max(Lc, 1)), **f64)
     env = torch.empty((2, rows, STOI_BANDS, max(Fb, 1)), **f64)
-    rho = torch.empty((rows, max(S, 1), STOI_BANDS), **f64)
+    seg = torch.empty((rows, max(S, 1)) + ((per,) if per > 1 else ()), **f64)
     d = torch.empty(rows, **f64)
-    check(lib.segan_stoi(_ptr(ref), _ptr(deg), _ptr(lens), rows, T, srate, _ptr(xr[0]), _ptr(xr[1]),
-                         _ptr(energy), _ptr(mask), _ptr(kept), _ptr(count), _ptr(xs[0]),
-                         _ptr(xs[1]), _ptr(env[0]), _ptr(env[1]), _ptr(rho), _ptr(d), _stream()),
-          'stoi')
-    return dict(xr=xr[0, :, :Ly], yr=xr[1, :, :Ly], energy=energy[:, :F], mask=mask[:, :F],
-                kept=kept[:, :F], count=count, xs=xs[0, :, :Lc], ys=xs[1, :, :Lc],
-                X=env[0, :, :, :Fb], Y=env[1, :, :, :Fb], rho=rho[:, :S], d=d,
-                dims=(Ly, F, Lc, Fb, S))
+    check(getattr(lib, 'segan_' + entry)(
+        _ptr(ref), _ptr(deg), _ptr(lens), rows, T, srate, _ptr(xr[0]), _ptr(xr[1]), _ptr(energy),
+        _ptr(mask), _ptr(kept), _ptr(count), _ptr(xs[0]), _ptr(xs[1]), _ptr(env[0]), _ptr(env[1]),
+        _ptr(seg), _ptr(d), _stream()), entry)
+    out = dict(xr=xr[0, :, :Ly], yr=xr[1, :, :Ly], energy=energy[:, :F], mask=mask[:, :F],
+               kept=kept[:, :F], count=count, xs=xs[0, :, :Lc], ys=xs[1, :, :Lc],
+               X=env[0, :, :, :Fb], Y=env[1, :, :, :Fb], d=d, dims=(Ly, F, Lc, Fb, S))
+    out[last] = seg[:, :S]
+    return out
+
+
+def stoi_stages(ref, deg, srate=16000, lengths=None):
+    """STOI (Taal et al.'s short-time objective intelligibility, DESIGN.md section 10) of each
+    row of ref / deg [rows, T] with every intermediate, fp64, on the device.  Row r is the signal
+    ref[r, :lengths[r]] (all T without `lengths`; host integers, a CUDA tensor is copied to the
+    host to be checked).  Returns a dict of device tensors, sized for T, of which each row uses
+    its own leading part: xr, yr [rows, Ly] (resampled to 10 kHz), energy, mask, kept
+    [rows, F] (clean frame energies in dB, keep mask, kept frame indices), count [rows] (M),
+    xs, ys [rows, Lc] (compacted), X, Y [rows, 15, Fb] (band envelopes), rho [rows, S, 15]
+    (segment correlations), d [rows]; and dims = (Ly, F, Lc, Fb, S)."""
+    return _stoi_run('stoi', 'rho', STOI_BANDS, ref, deg, srate, lengths)
 
 
 def stoi(ref, deg, srate=16000, lengths=None):
@@ -1155,6 +1162,21 @@ def stoi(ref, deg, srate=16000, lengths=None):
     silent-frame removal, a 0/0 correlation).  `lengths`: optional per-row valid sample counts
     (see stoi_stages).  srate: any integer from 4000 to 48000 Hz.  No device-to-host copy."""
     return stoi_stages(ref, deg, srate, lengths)['d']
+
+
+def estoi_stages(ref, deg, srate=16000, lengths=None):
+    """ESTOI (Jensen & Taal's extended STOI) of each row of ref / deg
+    [rows, T] with every intermediate: stoi_stages' dict (the same arguments, checks and stages
+    up to the band envelopes X, Y) with dm [rows, S], each segment's normalised-window inner
+    product / 30, in place of rho, and d [rows] their mean."""
+    return _stoi_run('estoi', 'dm', 1, ref, deg, srate, lengths)
+
+
+def estoi(ref, deg, srate=16000, lengths=None):
+    """ESTOI of each row of ref / deg [rows, T] (fp32 CUDA tensors) on the device: fp64 [rows],
+    NaN where it is undefined (a clean signal of digital silence, fewer than 30 band frames after
+    silent-frame removal).  Arguments as for `stoi`.  No device-to-host copy."""
+    return estoi_stages(ref, deg, srate, lengths)['d']
 
 
 ASL_THRESHOLDS = 15      # nbits - 1 thresholds 2^-15 .. 2^-1 (nbits = 16)

@@ -174,6 +174,15 @@ def composite_eval(ref, deg, pesq=None, workers=2):
             'wss': wss_m, 'llr': llr_m}
 
 
+def _same_shape_rows(what, ref, deg):
+    ref = _as_rows(ref, 'ref')
+    deg = _as_rows(deg, 'deg')
+    if ref.shape != deg.shape:
+        raise ValueError('{}: ref {} and deg {} differ in shape (signals of different lengths '
+                         'are not compared)'.format(what, tuple(ref.shape), tuple(deg.shape)))
+    return ref.float().contiguous(), deg.float().contiguous()
+
+
 def stoi(ref, deg, srate=SRATE, lengths=None):
     """STOI of each row of ref / deg ([rows, T] or [T] CUDA tensors of the same shape) on the
     device: fp64 tensor [rows].  srate: any integer from 4000 to 48000 Hz (resampled to 10 kHz on
@@ -184,9 +193,13 @@ def stoi(ref, deg, srate=SRATE, lengths=None):
     lengths raise ValueError, as stoi.m does.  NaN where STOI is undefined: a clean signal of
     digital silence, fewer than 30 band frames (about 0.4 s of non-silent speech) or a 0/0
     correlation."""
-    ref = _as_rows(ref, 'ref')
-    deg = _as_rows(deg, 'deg')
-    if ref.shape != deg.shape:
-        raise ValueError('stoi: ref {} and deg {} differ in shape (signals of different lengths '
-                         'are not compared)'.format(tuple(ref.shape), tuple(deg.shape)))
-    return ops.stoi(ref.float().contiguous(), deg.float().contiguous(), srate, lengths)
+    return ops.stoi(*_same_shape_rows('stoi', ref, deg), srate, lengths)
+
+
+def estoi(ref, deg, srate=SRATE, lengths=None):
+    """ESTOI (Jensen & Taal's extended STOI, which unlike STOI does not over-rate speech in
+    modulated noise such as babble) of each row of ref / deg: the contract of `stoi` (same
+    arguments, ValueError for different shapes, fp64 tensor [rows] on the device).  NaN where it
+    is undefined: a clean signal of digital silence or fewer than 30 band frames; a degenerate
+    band or frame of a window counts as uncorrelated (the zero rule)."""
+    return ops.estoi(*_same_shape_rows('estoi', ref, deg), srate, lengths)

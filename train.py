@@ -62,6 +62,10 @@ FLAGS = [
     ('--eval_stoi', dict(action='store_true', default=False,
                          help='the evaluation also reports STOI (short-time objective '
                               'intelligibility); the validation objective stays SSNR')),
+    ('--eval_estoi', dict(action='store_true', default=False,
+                          help='the evaluation also reports ESTOI (extended STOI, the measure '
+                               'to read beside PESQ under modulated noise such as babble); the '
+                               'validation objective stays SSNR')),
     ('--slice_workers', dict(type=int, default=1)),
     ('--num_workers', dict(type=int, default=1)),
     ('--no-cuda', dict(action='store_true', default=False)),
