@@ -2,7 +2,7 @@
 the clean wavs of the same names, on the MI355X: the reference's eval_noisy_performance.py.
 
     python eval_noisy_performance.py --test_wavs DIR --clean_wavs DIR --logfile FILE [--stoi]
-                                     [--estoi] [--resample]
+                                     [--estoi] [--fwsegsnr] [--cd] [--sisdr] [--resample]
 
 16 kHz wavs only (int16 files are scaled by 1/32768, float files used as they are), unless
 --resample converts files of other rates to 16 kHz on the GPU first (int16 files to int16, float
@@ -10,7 +10,10 @@ files to float32; --resample_zeros / --resample_beta set the filter); PESQ needs
 the external `pesqmain` on PATH (NaN, and so NaN CSIG / CBAK / COVL, without it).  --stoi adds
 a STOI column (quality.stoi on the GPU, both files truncated to their common length) and a final
 mean STOI line; --estoi does the same with an ESTOI column (quality.estoi, extended STOI), after
-STOI's when both are given."""
+STOI's when both are given.  --fwsegsnr, --cd and --sisdr add, in that order after them, the
+columns FWSEGSNR (quality.fwsegsnr, frequency-weighted segmental SNR in dB), CD
+(quality.cepstral_distance, LPC cepstrum distance) and SISDR (quality.si_sdr, scale-invariant SDR
+in dB) with their final mean lines; none of the three needs pesqmain."""
 import argparse
 import glob
 import os
@@ -48,19 +51,30 @@ def read_wav(path, opts=None):
     return x
 
 
+# the optional columns in their order: (column, flag, function of segan_pytorch_amd.quality)
+EXTRA = (('STOI', 'stoi', 'stoi'), ('ESTOI', 'estoi', 'estoi'),
+         ('FWSEGSNR', 'fwsegsnr', 'fwsegsnr'), ('CD', 'cd', 'cepstral_distance'),
+         ('SISDR', 'sisdr', 'si_sdr'))
+
+
+def header_line(opts):
+    return 'FILE CSIG CBAK COVL PESQ SSNR' + ''.join(
+        ' ' + name for name, flag, _ in EXTRA if getattr(opts, flag))
+
+
 def main(opts):
     if not torch.cuda.is_available():
         raise SystemExit('segan_pytorch_amd runs only on an MI355X (HIP) device; pass --cuda on a '
                          'GPU machine (there is no CPU fallback)')
-    from segan_pytorch_amd.quality import composite_eval, estoi, stoi
-    extra = [(name, fn) for name, fn, on in (('STOI', stoi, opts.stoi),
-                                             ('ESTOI', estoi, opts.estoi)) if on]
+    from segan_pytorch_amd import quality
+    from segan_pytorch_amd.quality import composite_eval
+    extra = [(name, getattr(quality, fn)) for name, flag, fn in EXTRA if getattr(opts, flag)]
     noisy_wavs = sorted(glob.glob(os.path.join(opts.test_wavs, '*.wav')))
-    metrics = {'csig': [], 'cbak': [], 'covl': [], 'STOI': [], 'ESTOI': []}
+    metrics = {'csig': [], 'cbak': [], 'covl': [], 'STOI': [], 'ESTOI': [], 'FWSEGSNR': [],
+               'CD': [], 'SISDR': []}
     timings = []
     with open(opts.logfile, 'w') as out_log:
-        out_log.write('FILE CSIG CBAK COVL PESQ SSNR' + ''.join(' ' + name for name, _ in extra) +
-                      '\n')
+        out_log.write(header_line(opts) + '\n')
         for n_i, noisy_wav in enumerate(noisy_wavs, start=1):
             bname = os.path.splitext(os.path.basename(noisy_wav))[0]
             clean_wav = os.path.join(opts.clean_wavs, bname + '.wav')
@@ -105,6 +119,12 @@ def build_parser():
     parser.add_argument('--estoi', action='store_true', default=False,
                         help='also compute ESTOI (extended STOI, the measure for modulated '
                              'noise such as babble)')
+    parser.add_argument('--fwsegsnr', action='store_true', default=False,
+                        help='also compute fwSNRseg (frequency-weighted segmental SNR, dB)')
+    parser.add_argument('--cd', action='store_true', default=False,
+                        help='also compute CD (LPC cepstrum distance)')
+    parser.add_argument('--sisdr', action='store_true', default=False,
+                        help='also compute SI-SDR (scale-invariant signal-to-distortion ratio, dB)')
     parser.add_argument('--resample', action='store_true', default=False,
                         help='convert wavs that are not 16 kHz to 16 kHz on the GPU instead of '
                              'refusing them')

@@ -440,6 +440,35 @@ int segan_stoi(const float* ref, const float* deg, const int* lengths, int rows,
 int segan_estoi(const float* ref, const float* deg, const int* lengths, int rows, int T, int srate,
                 double* xr, double* yr, double* energy, int* mask, int* kept, int* count,
                 double* xs, double* ys, double* X, double* Y, double* dm, double* d, void* stream);
+/* Three more objective measures, fp64, of row r = ref / deg [rows][T] restricted to its first
+ * lengths[r] samples (device int[rows], clamped to 0 .. T; NULL: all T); DESIGN.md section 13.
+ * Frames, window and srate limits are those of segan_wss / segan_llr; row r has
+ * segan_ssnr_frames(lengths[r], srate) frames of its own, and frames_out [rows][nframes]
+ * (nframes = segan_ssnr_frames(T, srate), at least one element) is NaN past them.  Every sum runs
+ * in a fixed order without atomics: a row's values do not depend on T, on the other rows or on
+ * the samples past its length, and two calls return the same bits.
+ *   segan_fwsegsnr: frequency-weighted segmental SNR.  Per frame the DFT magnitudes of all
+ *     nfft/2 bins, each spectrum divided by its sum, through WSS's 25 critical-band filters
+ *     (ce, pe); sum(W snr) / sum(W) with W = ce^0.2, snr = 10 log10(ce^2 / max((ce - pe)^2,
+ *     2^-52)), clipped to [-10, 35]; NaN where that is not finite (a frame of digital silence in
+ *     either signal).  row_out[rows]: the mean of the row's finite frames, NaN without any.
+ *   segan_cepdist: LPC cepstrum distance.  LLR's lags and order (16 for srate >= 10000, else 10),
+ *     Levinson-Durbin in fp64 without LLR's fp32 rounding, c_1 = -a_1, c_n = -a_n - (1/n)
+ *     sum_{k<n} k c_k a_{n-k}; min(10, 10 sqrt(2) / ln 10 * ||c(ref) - c(deg)||_2); NaN where
+ *     either frame has no energy.  Nothing is launched when nframes is 0.
+ *   segan_sisdr: scale-invariant SDR (Le Roux et al. 2019) of whole rows.  Both means removed,
+ *     alpha = <s,x> / <s,s>, e = alpha s - x summed sample by sample in a second pass;
+ *     row_out[rows] = 10 log10(alpha^2 <s,s> / <e,e>): NaN where <s,s> is 0, +inf where <e,e> is.
+ *     ws: workspace of rows * (4 * ceil(T / SEGAN_SISDR_SPAN) + 4) doubles.
+ * Added without a change of SEGAN_ABI_VERSION: the exports are purely additive, every earlier
+ * entry keeps its signature and its results. */
+#define SEGAN_SISDR_SPAN 4096
+int segan_fwsegsnr(const float* ref, const float* deg, const int* lengths, int rows, int T,
+                   int srate, double* frames_out, double* row_out, void* stream);
+int segan_cepdist(const float* ref, const float* deg, const int* lengths, int rows, int T,
+                  int srate, double* frames_out, void* stream);
+int segan_sisdr(const float* ref, const float* deg, const int* lengths, int rows, int T,
+                double* row_out, double* ws, void* stream);
 
 /* ---- on-the-fly additive noise (the reference's Additive, utils.py:43-297)
  * fp64 arithmetic on fp32 rows x / clean [rows][T], row r restricted to its first lengths[r]

@@ -5,6 +5,10 @@ utterance like eval_noisy_performance.py, with a device synchronise; prints one 
     python scripts/bench_quality.py            # MI355X
     python scripts/bench_quality.py --cpu-ref N  # the reference's numpy CompositeEval on N of the
                                                  # same utterances (needs the reference checkout)
+    python scripts/bench_quality.py --measures   # and, in the same run, ONE batched call each of
+        # quality.fwsegsnr / cepstral_distance / si_sdr over the set padded to its longest
+        # utterance with `lengths`, beside quality.stoi's batched call; the JSON line also goes to
+        # --out (profiles/measures_bench.json)
 """
 import argparse
 import json
@@ -34,6 +38,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--cpu-ref', type=int, default=0)
     ap.add_argument('--warmup', type=int, default=20)
+    ap.add_argument('--measures', action='store_true',
+                    help='also time the batched fwSNRseg + CD + SI-SDR call (and STOI\'s)')
+    ap.add_argument('--batch-reps', type=int, default=5)
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'measures_bench.json'))
     args = ap.parse_args()
     utts = utterances()
     if args.cpu_ref:
@@ -61,10 +69,51 @@ def main():
         r = composite_eval(c, d, pesq=2.5)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    print(json.dumps({'leg': 'mi355x', 'utts': len(dev), 'seconds': dt, 'utts_per_s': len(dev) / dt,
-                      'mean_s_per_utt': dt / len(dev),
-                      'mean_audio_s': float(np.mean([len(c) for c, _ in utts])) / 16000,
-                      'last_csig': float(r['csig'][0])}))
+    out = {'leg': 'mi355x', 'utts': len(dev), 'seconds': dt, 'utts_per_s': len(dev) / dt,
+           'mean_s_per_utt': dt / len(dev),
+           'mean_audio_s': float(np.mean([len(c) for c, _ in utts])) / 16000,
+           'last_csig': float(r['csig'][0])}
+    if args.measures:
+        out['measures'] = batched_measures(torch, utts, args.batch_reps)
+        with open(args.out, 'w') as f:
+            f.write(json.dumps(out) + '\n')
+    print(json.dumps(out))
+
+
+def batched_measures(torch, utts, reps):
+    """Seconds of one batched call (after one warm-up call, mean of `reps`, up to a device
+    synchronise) of the three measures together, of each alone, and of quality.stoi."""
+    from segan_pytorch_amd import quality
+    lengths = [len(c) for c, _ in utts]
+    ref = torch.zeros(len(utts), max(lengths))
+    deg = torch.zeros(len(utts), max(lengths))
+    for i, (c, d) in enumerate(utts):
+        ref[i, :len(c)] = torch.from_numpy(c)
+        deg[i, :len(d)] = torch.from_numpy(d)
+    ref, deg = ref.cuda(), deg.cuda()
+
+    def timed(fn):
+        res = fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            res = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / reps, res
+
+    legs = {'fwsegsnr': lambda: quality.fwsegsnr(ref, deg, lengths=lengths),
+            'cd': lambda: quality.cepstral_distance(ref, deg, lengths=lengths),
+            'sisdr': lambda: quality.si_sdr(ref, deg, lengths=lengths)}
+    out = {}
+    dt, res = timed(lambda: [fn() for fn in legs.values()])
+    out['batched_seconds'] = dt
+    out['batched_utts_per_s'] = len(utts) / dt
+    for (k, fn), v in zip(legs.items(), res):
+        out[k + '_seconds'] = timed(fn)[0]
+        out['mean_' + k] = float(v[torch.isfinite(v)].mean())
+        out[k + '_nonfinite_rows'] = int((~torch.isfinite(v)).sum())
+    out['stoi_batched_seconds'] = timed(lambda: quality.stoi(ref, deg, lengths=lengths))[0]
+    return out
 
 
 if __name__ == '__main__':

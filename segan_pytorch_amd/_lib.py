@@ -100,6 +100,9 @@ SIGNATURES = {
     'segan_stoi_dims': (c_int, [c_int, c_int, POINTER(c_int)]),
     'segan_stoi': (c_int, [_P, _P, _P, c_int, c_int, c_int] + [_P] * 13),
     'segan_estoi': (c_int, [_P, _P, _P, c_int, c_int, c_int] + [_P] * 13),
+    'segan_fwsegsnr': (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
+    'segan_cepdist': (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P]),
+    'segan_sisdr': (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P]),
     'segan_asl_p56': (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     'segan_additive_mix': (c_int, [_P, _P, _P, c_int64, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P]),
     'segan_resample_plan': (c_int, [c_int, c_int, c_int, c_double, POINTER(c_int), POINTER(c_int), _P, c_int]),

@@ -422,7 +422,9 @@ class SEGAN(Model):
         comes from the external `pesqmain` binary (run in `opts.eval_workers` threads, at most
         16); without it on PATH pesq / csig / cbak / covl are NaN.  With `opts.eval_stoi` set (train.py
         --eval_stoi) a key 'stoi' (quality.stoi, 16 kHz) is added, computed on the same signals;
-        with `opts.eval_estoi` (train.py --eval_estoi) a key 'estoi' (quality.estoi) likewise.
+        with `opts.eval_estoi` (train.py --eval_estoi) a key 'estoi' (quality.estoi) likewise,
+        and with `opts.eval_fwsegsnr` / `eval_cd` / `eval_sisdr` the keys 'fwsegsnr', 'cd',
+        'sisdr' (quality.fwsegsnr, quality.cepstral_distance, quality.si_sdr).
         De-emphasis runs along time (the reference applies it along axis 0 of the [B, T] batch,
         model.py:474-477)."""
         from .. import ops, quality
@@ -430,8 +432,13 @@ class SEGAN(Model):
         self.D.eval()
         with_stoi = bool(getattr(opts, 'eval_stoi', False))
         with_estoi = bool(getattr(opts, 'eval_estoi', False))
+        more = [(k, fn) for k, fn in (('fwsegsnr', quality.fwsegsnr),
+                                      ('cd', quality.cepstral_distance),
+                                      ('sisdr', quality.si_sdr))
+                if bool(getattr(opts, 'eval_' + k, False))]
         keys = ('ssnr', 'snr', 'pesq', 'csig', 'cbak', 'covl', 'wss', 'llr') + (
-            ('stoi',) if with_stoi else ()) + (('estoi',) if with_estoi else ())
+            ('stoi',) if with_stoi else ()) + (('estoi',) if with_estoi else ()) + tuple(
+                k for k, _ in more)
         evals = {k: [] for k in keys}
         noisy_evals = {k: [] for k in keys}
         workers = getattr(opts, 'eval_workers', 2)
@@ -456,6 +463,8 @@ class SEGAN(Model):
                         dst['stoi'] += quality.stoi(c, d).cpu().tolist()
                     if with_estoi:
                         dst['estoi'] += quality.estoi(c, d).cpu().tolist()
+                    for k, fn in more:
+                        dst[k] += fn(c, d).cpu().tolist()
                 if bidx >= max_samples:
                     break
         self.G.train()

@@ -1179,6 +1179,80 @@ def estoi(ref, deg, srate=16000, lengths=None):
     return estoi_stages(ref, deg, srate, lengths)['d']
 
 
+SISDR_SPAN = 4096        # SEGAN_SISDR_SPAN (include/segan_hip.h): samples per partial sum
+
+
+def _measure_args(what, ref, deg, lengths):
+    """The argument checks of ops.stoi for the measures with per-row lengths: fp32 CUDA [rows, T]
+    of one shape, host integers 1 <= lengths[r] <= T.  Returns (rows, T, device int32 lengths or
+    None)."""
+    _chk(ref, 'ref', 2)
+    _chk(deg, 'deg', 2)
+    if ref.shape != deg.shape:
+        raise ValueError('{}: shapes differ {} vs {}'.format(what, tuple(ref.shape), tuple(deg.shape)))
+    rows, T = ref.shape
+    if rows < 1 or T < 1:
+        raise ValueError('{}: empty input {}'.format(what, tuple(ref.shape)))
+    lens = None
+    if lengths is not None:
+        host = torch.as_tensor(lengths).detach().cpu()
+        lens = _row_lengths(what, host, rows, T, ref.device)
+        if int(host.min()) < 1:
+            raise ValueError('{}: lengths must lie in 1 .. {}, got {}'.format(what, T, host.tolist()))
+    return rows, T, lens
+
+
+def _measure_srate(what, srate):
+    return _int_arg(srate, what + ': srate', 1, 1 << 20)
+
+
+def fwsegsnr(ref, deg, srate=16000, lengths=None):
+    """Frequency-weighted segmental SNR (Hu & Loizou's fwSNRseg) of each row
+    of ref / deg [rows, T] (fp32 CUDA tensors) on the device, on the frames of `wss`.  Row r is
+    ref[r, :lengths[r]] (all T without `lengths`; host integers as in `stoi`).  Returns (frames
+    [rows, nframes] fp64, clipped to [-10, 35], NaN where a frame of either signal is digital
+    silence and past the row's own frame count; value [rows] fp64, the mean of the row's finite
+    frames, NaN without any).  No device-to-host copy."""
+    rows, T, lens = _measure_args('fwsegsnr', ref, deg, lengths)
+    srate = _measure_srate('fwsegsnr', srate)
+    lib = _lib.load()
+    nf = lib.segan_ssnr_frames(T, srate)
+    frames = torch.empty((rows, max(nf, 1)), device=ref.device, dtype=torch.float64)
+    value = torch.empty(rows, device=ref.device, dtype=torch.float64)
+    check(lib.segan_fwsegsnr(_ptr(ref), _ptr(deg), _ptr(lens), rows, T, srate, _ptr(frames),
+                             _ptr(value), _stream()), 'fwsegsnr')
+    return frames[:, :nf], value
+
+
+def cepstral_distance(ref, deg, srate=16000, lengths=None):
+    """Per-frame LPC cepstrum distance (Hu & Loizou's CD) of each row of
+    ref / deg [rows, T] on the device, on the frames and lags of `llr` with an fp64 Levinson
+    recursion: fp64 [rows, nframes], at most 10, NaN where a frame of either signal has no energy
+    and past the row's own frame count.  `lengths` as in `fwsegsnr`."""
+    rows, T, lens = _measure_args('cepstral_distance', ref, deg, lengths)
+    srate = _measure_srate('cepstral_distance', srate)
+    lib = _lib.load()
+    nf = lib.segan_ssnr_frames(T, srate)
+    frames = torch.empty((rows, max(nf, 1)), device=ref.device, dtype=torch.float64)
+    check(lib.segan_cepdist(_ptr(ref), _ptr(deg), _ptr(lens), rows, T, srate, _ptr(frames),
+                            _stream()), 'cepstral_distance')
+    return frames[:, :nf]
+
+
+def si_sdr(ref, deg, lengths=None):
+    """Scale-invariant SDR (Le Roux et al. 2019) in dB of each row of ref / deg [rows, T] on the
+    device: fp64 [rows]; NaN where the clean row (mean removed) has no energy, +inf where the
+    processed row is a scaled and shifted copy of it to the last bit.  Fixed summation order: two
+    calls return the same bits.  `lengths` as in `fwsegsnr`.  No device-to-host copy."""
+    rows, T, lens = _measure_args('si_sdr', ref, deg, lengths)
+    out = torch.empty(rows, device=ref.device, dtype=torch.float64)
+    ws = torch.empty(rows * (4 * ((T + SISDR_SPAN - 1) // SISDR_SPAN) + 4), device=ref.device,
+                     dtype=torch.float64)
+    check(_lib.load().segan_sisdr(_ptr(ref), _ptr(deg), _ptr(lens), rows, T, _ptr(out), _ptr(ws),
+                                  _stream()), 'si_sdr')
+    return out
+
+
 ASL_THRESHOLDS = 15      # nbits - 1 thresholds 2^-15 .. 2^-1 (nbits = 16)
 ADDITIVE_CAP = 1         # status bits of asl_p56 / additive_mix (include/segan_hip.h)
 ADDITIVE_PN0 = 2

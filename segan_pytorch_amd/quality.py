@@ -203,3 +203,35 @@ def estoi(ref, deg, srate=SRATE, lengths=None):
     is undefined: a clean signal of digital silence or fewer than 30 band frames; a degenerate
     band or frame of a window counts as uncorrelated (the zero rule)."""
     return ops.estoi(*_same_shape_rows('estoi', ref, deg), srate, lengths)
+
+
+def fwsegsnr(ref, deg, srate=SRATE, lengths=None):
+    """Frequency-weighted segmental SNR (fwSNRseg) of each row of ref / deg
+    ([rows, T] or [T] CUDA tensors of the same shape; `lengths` as for `stoi`) on the device: fp64
+    tensor [rows], the mean of the row's finite frame values.  NaN where no frame is finite: fewer
+    samples than one frame (T < win + hop, 600 at 16 kHz) or digital silence throughout."""
+    return ops.fwsegsnr(*_same_shape_rows('fwsegsnr', ref, deg), srate, lengths)[1]
+
+
+def cepstral_distance(ref, deg, srate=SRATE, lengths=None):
+    """LPC cepstrum distance (CD) of each row of ref / deg (the contract of
+    `fwsegsnr`): fp64 tensor [rows], the 0.95-trimmed mean of the row's finite frame values
+    (ascending, the first trimmed_count(n_finite) of them).  NaN where no frame is finite."""
+    frames = ops.cepstral_distance(*_same_shape_rows('cepstral_distance', ref, deg), srate, lengths)
+    rows, nf = frames.shape
+    if nf == 0:
+        return torch.full((rows,), math.nan, device=frames.device, dtype=torch.float64)
+    # NaN sorts last: the first n_finite of each sorted row are its finite values
+    srt = torch.sort(frames, dim=1).values
+    n_fin = torch.isfinite(frames).sum(dim=1)
+    keep = torch.tensor([trimmed_count(n) for n in range(nf + 1)], device=frames.device)[n_fin]
+    sel = torch.arange(nf, device=frames.device).unsqueeze(0) < keep.unsqueeze(1)
+    total = torch.where(sel, srt, torch.zeros_like(srt)).sum(dim=1)
+    return total / keep        # 0 / 0: NaN without a finite frame
+
+
+def si_sdr(ref, deg, lengths=None):
+    """Scale-invariant SDR in dB (Le Roux et al. 2019) of each row of ref / deg (shapes and
+    `lengths` as for `stoi`): fp64 tensor [rows].  NaN for a clean signal without energy once its
+    mean is removed, +inf where the processed signal is an exact scaled, shifted copy."""
+    return ops.si_sdr(*_same_shape_rows('si_sdr', ref, deg), lengths)

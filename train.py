@@ -66,6 +66,13 @@ FLAGS = [
                           help='the evaluation also reports ESTOI (extended STOI, the measure '
                                'to read beside PESQ under modulated noise such as babble); the '
                                'validation objective stays SSNR')),
+    ('--eval_fwsegsnr', dict(action='store_true', default=False,
+                             help='the evaluation also reports fwSNRseg (frequency-weighted '
+                                  'segmental SNR); the validation objective stays SSNR')),
+    ('--eval_cd', dict(action='store_true', default=False,
+                       help='the evaluation also reports CD (LPC cepstrum distance)')),
+    ('--eval_sisdr', dict(action='store_true', default=False,
+                          help='the evaluation also reports SI-SDR (scale-invariant SDR)')),
     ('--slice_workers', dict(type=int, default=1)),
     ('--num_workers', dict(type=int, default=1)),
     ('--no-cuda', dict(action='store_true', default=False)),
