@@ -548,6 +548,65 @@ int segan_resample(const void* x, int x_dtype, const int* lengths, int rows, int
                    int rate_out, int zeros, double beta, void* y, int y_dtype, int Ly_max,
                    int* out_lengths, int* nclip, int* ws, void* stream);
 
+/* ---- on-the-fly reverberation (room impulse responses) ------------------
+ * Row r of x [rows][T] is convolved with its own RIR h (L taps, direct path at tap d, h[d] = 1):
+ *   y[n] = sum_{k < L} h[k] x[n + d - k],  n = -1 .. len_r - 1,
+ * with x[-1] = prev[r] (0 without prev), x zero elsewhere outside 0 .. len_r - 1 (len_r =
+ * lengths[r] clamped to 0 .. T; NULL: T).  y[-1] is returned as prev_out[r]; y[n] = 0 from len_r.
+ * Uniformly partitioned overlap-save convolution: partition P = SEGAN_REVERB_P samples, transform
+ * size 2P, both transforms as unsplit segan_gemm products against a shared basis.  A real 2P
+ * spectrum is packed into 2P floats: column f = Re X[f] (f = 0 .. P), column P + f = Im X[f]
+ * (f = 1 .. P-1).  No atomics: a row's result is bitwise independent of the other rows, of its
+ * position and of the batch size.
+ *   segan_reverb_dims (host only): dims[8] = (P, blocks per row NB, frames M of the two products,
+ *     ceil(max_taps / P), floats of the staging buffer, of a spectrum buffer, of the inverse
+ *     transform, of the whole workspace of segan_reverb_rows).  NB depends on T and max_delay only.
+ *   segan_reverb_basis: fwd [2P][2P] (time x column) and inv [2P][P] (column x output P .. 2P-1),
+ *     from fp64 sincospi of exactly reduced arguments.
+ *   segan_reverb_bank: taps [n_parts][P] (every RIR zero-padded to whole partitions, concatenated)
+ *     -> H [n_parts][2P], the spectra of the partitions zero-padded to 2P: 8 bytes per padded tap.
+ *   table int[n_rirs][4] = (first partition, partitions, taps, d) per RIR; rir_ids int[rows].
+ *   segan_reverb_stage: xs [(frames + 1) P]: a zero block, then per row NB blocks = (P-1 zeros,
+ *     prev), x, zeros; frame g of the forward product starts at xs + g P (sam = P, sak = 1).
+ *   segan_reverb_forward / segan_reverb_inverse: X [frames][2P] = frames x fwd; yt [frames][P] =
+ *     Y x inv with the contraction in blocks of 64 added in order (one accumulator over all 2P
+ *     terms of an inverse transform doubles the error against fp64).
+ *   segan_reverb_fdl: Y[r, a] = sum_{b < partitions, b <= a} X[r, a-b] H[first + b], complex per
+ *     bin, b ascending, X / Y [frames][2P] with frame r NB + a.
+ *   segan_reverb_finish: y[r][n] = yt[r NB P + P + n + d], prev_out[r] (may be NULL) = the same at
+ *     n = -1, status int[rows]: SEGAN_REVERB_ST_RIR = the id is outside the table, or the table
+ *     entry is outside the bank of bank_parts partitions or inconsistent; SEGAN_REVERB_ST_DELAY =
+ *     d exceeds the max_delay the blocks were sized for.  A flagged row reads nothing of the bank
+ *     or the transforms: y = x, prev_out = prev.
+ *   segan_reverb_rows: the whole chain (stage, product, delay line, product, finish) on `stream`;
+ *     ws: workspace of dims[7] floats, 16-byte aligned.
+ * Added without a change of SEGAN_ABI_VERSION: the exports are purely additive. */
+#ifndef SEGAN_REVERB_P
+#define SEGAN_REVERB_P 128   /* compile-time; the analytic start sqrt(L/2), not yet measured against 64 / 256 */
+#endif
+#define SEGAN_REVERB_ST_RIR 1
+#define SEGAN_REVERB_ST_DELAY 2
+#define SEGAN_REVERB_MAX_ROWS 32768
+#define SEGAN_REVERB_MAX_FRAMES 8000000
+int segan_reverb_dims(int rows, int T, int max_delay, int max_taps, int64_t* dims);
+int segan_reverb_basis(float* fwd, float* inv, void* stream);
+int segan_reverb_bank(const float* taps, int64_t n_parts, const float* fwd, float* H, void* stream);
+int segan_reverb_stage(const float* x, const int* lengths, const float* prev, float* xs, int rows,
+                       int T, int blocks, int frames, void* stream);
+int segan_reverb_forward(const float* xs, const float* fwd, float* X, int frames, void* stream);
+int segan_reverb_inverse(const float* Y, const float* inv, float* yt, int frames, void* stream);
+int segan_reverb_fdl(const float* X, const float* H, int64_t bank_parts, const int* rir_ids,
+                     const int* table, int n_rirs, float* Y, int rows, int T, int blocks,
+                     int frames, void* stream);
+int segan_reverb_finish(const float* yt, const float* x, const int* lengths, const float* prev,
+                        int64_t bank_parts, const int* rir_ids, const int* table, int n_rirs,
+                        float* y, float* prev_out, int* status, int rows, int T, int blocks,
+                        int frames, void* stream);
+int segan_reverb_rows(const float* x, const int* lengths, const float* prev, const float* H,
+                      int64_t bank_parts, const int* rir_ids, const int* table, int n_rirs,
+                      const float* fwd, const float* inv, int rows, int T, int max_delay, float* ws,
+                      int64_t ws_floats, float* y, float* prev_out, int* status, void* stream);
+
 /* ---- optimizers (model.py:219-228) ---------------------------------------------------- */
 /* torch.optim.RMSprop (no momentum, not centered): sq = alpha*sq + (1-alpha)*g*g;
  * p -= lr * g / (sqrt(sq) + eps), over a flat arena of n floats. */

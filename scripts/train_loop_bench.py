@@ -9,7 +9,9 @@ per-batch timing (the reference's `btime` excludes them too: model.py:322-348).
     python scripts/train_loop_bench.py [--items 3000] [--epochs 6]  > profiles/rNN_train_loop.json
 
 `--additive` (opt-in) adds `--additive_noises` over two synthetic 30 s noise wavs: every item's noisy
-row is mixed on the loader's side stream.
+row is mixed on the loader's side stream.  `--reverb` (opt-in) adds
+`--reverb_rirs` over four synthetic 4000-tap impulse responses: every item's clean wave is
+reverberated on the side stream first.
 """
 import argparse
 import json
@@ -30,6 +32,9 @@ ap.add_argument('--batch', type=int, default=300)
 ap.add_argument('--tmp', default='/tmp/segan_train_loop')
 ap.add_argument('--additive', action='store_true',
                 help='mix noise into every item on the fly (train.py --additive_noises)')
+ap.add_argument('--reverb', action='store_true',
+                help='reverberate every item on the fly (train.py --reverb_rirs)')
+ap.add_argument('--reverb_taps', type=int, default=4000)
 args = ap.parse_args()
 
 os.makedirs(args.tmp, exist_ok=True)
@@ -54,6 +59,15 @@ if args.additive:
         wavfile.write(os.path.join(ndir, 'n{}.wav'.format(i)), 16000,
                       (rng.randn(30 * 16000) * 1500).astype(np.int16))
     extra = ['--additive_noises', ndir]
+if args.reverb:
+    from scipy.io import wavfile
+    rdir = os.path.join(args.tmp, 'rirs')
+    os.makedirs(rdir, exist_ok=True)
+    for i in range(4):
+        h = rng.randn(args.reverb_taps) * np.exp(-np.arange(args.reverb_taps) / (args.reverb_taps / 6.0))
+        h[10 + i] = 4.0
+        wavfile.write(os.path.join(rdir, 'r{}.wav'.format(i)), 16000, np.rint(h * 6000).astype(np.int16))
+    extra = extra + ['--reverb_rirs', rdir, '--reverb_max_taps', str(args.reverb_taps)]
 
 import train
 from segan_pytorch_amd.models import core
@@ -92,7 +106,7 @@ ms = 1e3 * (t1 - state['t0']) / timed
 out = {'what': 'train.py --pcm_shard (default SEGAN+ net, batch {}, RMSprop, host z, int16 shard '
                'through worker gathers + GPU prep): {} epochs of {} batches, the first epoch is '
                'warm-up, device-synchronised clock around the rest'.format(args.batch, args.epochs, per_epoch),
-       'additive': bool(args.additive), 'ms_per_batch': ms, 'chunks_per_s': args.batch * 1e3 / ms, 'batches_timed': timed}
+       'additive': bool(args.additive), 'reverb': bool(args.reverb), 'ms_per_batch': ms, 'chunks_per_s': args.batch * 1e3 / ms, 'batches_timed': timed}
 try:
     import glob
     b = json.load(open(sorted(glob.glob(os.path.join(ROOT, 'profiles', 'r[0-9][0-9]_bench_line.json')))[-1]))

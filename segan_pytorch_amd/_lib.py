@@ -111,6 +111,17 @@ SIGNATURES = {
                                c_int, _P, _P, _P, _P]),
     'segan_pcm16_wave': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
     'segan_preemph_rows': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_double, _P]),
+    'segan_reverb_dims': (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int64)]),
+    'segan_reverb_basis': (c_int, [_P, _P, _P]),
+    'segan_reverb_bank': (c_int, [_P, c_int64, _P, _P, _P]),
+    'segan_reverb_stage': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    'segan_reverb_forward': (c_int, [_P, _P, _P, c_int, _P]),
+    'segan_reverb_inverse': (c_int, [_P, _P, _P, c_int, _P]),
+    'segan_reverb_fdl': (c_int, [_P, _P, c_int64, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, _P]),
+    'segan_reverb_finish': (c_int, [_P, _P, _P, _P, c_int64, _P, _P, c_int, _P, _P, _P, c_int, c_int,
+                                    c_int, c_int, _P]),
+    'segan_reverb_rows': (c_int, [_P, _P, _P, _P, c_int64, _P, _P, c_int, _P, _P, c_int, c_int, c_int,
+                                  _P, c_int64, _P, _P, _P, _P]),
     'segan_rmsprop_step': (c_int, [_P, _P, _P, c_float, c_float, c_float, c_int64, _P]),
     'segan_adam_step': (c_int, [_P, _P, _P, _P, c_float, c_double, c_double, c_float, c_int, c_int64,
                                 _P]),

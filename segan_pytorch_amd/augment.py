@@ -1,6 +1,8 @@
 """On-the-fly additive noise at a target SNR on the MI355X: the reference's
 `Additive` (segan/utils.py:43-297) with the level measurement (ITU-T P.56 method B) and the mix as
-HIP kernels (`ops.asl_p56`, `ops.additive_mix`), batched."""
+HIP kernels (`ops.asl_p56`, `ops.additive_mix`), batched.  And on-the-fly reverberation (section
+14): `Reverb` convolves each row with a room impulse response of an `RIRBank`
+(`ops.reverb_rows`)."""
 import glob
 import os
 
@@ -187,6 +189,166 @@ class Additive(object):
         x = torch.from_numpy(np.ascontiguousarray(np.asarray(wav, dtype=np.float32).reshape(1, -1)))
         noisy, _ = self.mix(x.cuda(), srate=srate)
         return noisy[0].cpu().type(torch.FloatTensor)
+
+
+class RIRBank(object):
+    """Room impulse responses, normalised once on the host in float64: each is cut to `max_taps`,
+    d = argmax |h| (first occurrence) is its direct path, h / h[d] is rounded to fp32 once — the
+    direct path stays time-aligned with the dry signal and has gain exactly 1 (a negative peak
+    divides through).  An RIR without a non-zero tap is refused.  `RIRBank(list_of_arrays)` takes
+    arrays as `NoiseBank` does; `RIRBank.from_dir(dir)` reads every *.wav of a directory with the
+    same reader and the same optional GPU rate conversion (`target_rate`).
+
+    `taps`, `delays`: int64 arrays, per RIR.  `data(device)`: the bank on a HIP device, built on
+    first use — the spectra of the RIRs' partitions (`ops.reverb_bank`: P = ops.REVERB_P taps each,
+    8 bytes per tap of the RIR padded to a multiple of P, 128 KiB for 16384 taps) and the
+    per-RIR table (first partition, partitions, taps, d)."""
+
+    def __init__(self, arrays, files=None, max_taps=16384):
+        max_taps = int(max_taps)
+        if max_taps < 1:
+            raise ValueError('RIRBank: max_taps must be positive, got {}'.format(max_taps))
+        arrays = list(arrays)
+        if len(arrays) == 0:
+            raise ValueError('[!] No impulse responses found in {}'.format(
+                files if files is not None else arrays))
+        self.files = list(files) if files is not None else ['rir{}'.format(i)
+                                                            for i in range(len(arrays))]
+        self.max_taps = max_taps
+        self.rirs, delays = [], []
+        for name, a in zip(self.files, arrays):
+            h, d = self._normalise(self._as_float64(a), max_taps, name)
+            self.rirs.append(h)
+            delays.append(d)
+        self.taps = np.array([len(h) for h in self.rirs], dtype=np.int64)
+        self.delays = np.array(delays, dtype=np.int64)
+        P = ops.REVERB_P
+        self.partitions = (self.taps + P - 1) // P
+        self.offsets = np.concatenate(([0], np.cumsum(self.partitions))).astype(np.int64)
+        if int(self.offsets[-1]) >= 1 << 31:
+            raise ValueError('RIRBank: {} partitions do not fit the table'.format(self.offsets[-1]))
+        self._dev = {}
+
+    @staticmethod
+    def _as_float64(a):
+        if isinstance(a, torch.Tensor):
+            a = a.detach().cpu().numpy()
+        a = np.asarray(a)
+        if a.dtype == np.int16:
+            a = a.astype(np.float64) / 32768.0
+        elif not np.issubdtype(a.dtype, np.floating):
+            raise TypeError('RIRBank: impulse responses must be float or int16 arrays, got {}'.format(
+                a.dtype))
+        if a.ndim == 2:      # [samples, channels] as scipy reads it
+            a = a.astype(np.float64).mean(axis=1)
+        return np.ascontiguousarray(a.reshape(-1), dtype=np.float64)
+
+    @staticmethod
+    def _normalise(h, max_taps, name):
+        # restated by scripts/reverb_oracle.py:normalise (the oracle's copy): keep the two alike
+        h = h[:max_taps]
+        if h.size == 0 or not np.any(h != 0):
+            raise ValueError('RIRBank: {} has no non-zero tap within max_taps={}'.format(
+                name, max_taps))
+        if not np.all(np.isfinite(h)):
+            raise ValueError('RIRBank: {} has a non-finite tap'.format(name))
+        d = int(np.argmax(np.abs(h)))
+        return (h / h[d]).astype(np.float32), d
+
+    @classmethod
+    def from_dir(cls, rirs_dir, target_rate=None, max_taps=16384, resample_zeros=ops.RESAMPLE_ZEROS,
+                 resample_beta=ops.RESAMPLE_BETA):
+        from scipy.io import wavfile
+        names = sorted(glob.glob(os.path.join(rirs_dir, '*.wav')))
+        if len(names) == 0:
+            raise ValueError('[!] No impulse responses found in {}'.format(rirs_dir))
+        read = [wavfile.read(n) for n in names]
+        wavs = [w for _, w in read]
+        if target_rate is not None:
+            from .resample import resample_many
+            wavs, _ = resample_many(wavs, [r for r, _ in read], target_rate, resample_zeros,
+                                    resample_beta)
+        return cls(wavs, files=names, max_taps=max_taps)
+
+    def __len__(self):
+        return len(self.rirs)
+
+    def padded(self):
+        """The RIRs zero-padded to whole partitions and concatenated: fp32 [partitions, P]."""
+        P = ops.REVERB_P
+        out = np.zeros((int(self.offsets[-1]), P), dtype=np.float32)
+        flat = out.reshape(-1)
+        for h, o in zip(self.rirs, self.offsets[:-1]):
+            flat[o * P:o * P + len(h)] = h
+        return out
+
+    def data(self, device):
+        """`ops.ReverbBankData` of the bank on `device` (a HIP device; built once per device)."""
+        device = torch.device(device)
+        if device.type != 'cuda':
+            raise RuntimeError('RIRBank: segan_pytorch_amd runs only on an MI355X (HIP) device; '
+                               'there is no CPU path')
+        if device.index is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        if device not in self._dev:
+            with torch.cuda.device(device):
+                H = ops.reverb_bank(torch.from_numpy(self.padded()).to(device))
+                table = np.stack([self.offsets[:-1], self.partitions, self.taps, self.delays], axis=1)
+                table = torch.from_numpy(np.ascontiguousarray(table, dtype=np.int32)).to(device)
+                torch.cuda.current_stream(device).synchronize()      # other streams use it next
+            self._dev[device] = ops.ReverbBankData(H, table, int(self.delays.max()))
+        return self._dev[device]
+
+
+class Reverb(object):
+    """On-the-fly reverberation.  `rirs`: a directory of wavs, a list of
+    arrays or an `RIRBank`.  `apply(clean[B, T])` convolves each row with an RIR drawn uniformly
+    from the bank, on the device; `__call__(wav)` does one waveform and returns a CPU FloatTensor,
+    like `Additive.__call__`.  The direct path of every RIR has gain 1 and stays aligned with the
+    dry signal, which remains the regression target.  Every slice is reverberated as if silence
+    preceded it: no tail is carried over from earlier slices of the utterance.  Draws come from a
+    numpy Generator owned by the object (`seed`)."""
+
+    def __init__(self, rirs, seed=None, max_taps=16384, target_rate=None):
+        if isinstance(rirs, RIRBank):
+            self.bank = rirs
+        elif isinstance(rirs, (str, os.PathLike)):
+            self.rirs_dir = rirs
+            self.bank = RIRBank.from_dir(rirs, target_rate=target_rate, max_taps=max_taps)
+        else:
+            self.bank = RIRBank(rirs, max_taps=max_taps)
+        self.rng = np.random.default_rng(seed)
+
+    def draw(self, rng, rows, rir_ids=None):
+        if rir_ids is None:
+            return rng.integers(len(self.bank), size=rows).astype(np.int64)
+        ids = np.asarray(rir_ids, dtype=np.int64).reshape(-1)
+        if len(ids) != rows or (ids < 0).any() or (ids >= len(self.bank)).any():
+            raise ValueError('Reverb: {} rir ids in 0 .. {} expected, got {}'.format(
+                rows, len(self.bank) - 1, ids.tolist()))
+        return ids
+
+    def apply(self, clean, generator=None, rir_ids=None, lengths=None, prev=None):
+        """clean [B, T] (fp32 CUDA) -> (wet [B, T], info).  `generator`: a numpy Generator used
+        instead of the object's; `rir_ids` (per row) replaces the draw.  info: rir_ids, taps,
+        delays (numpy, host), prev (device: the reverberant sample preceding each row) and status
+        (device int32, `ops.reverb_rows`)."""
+        ops._chk(clean, 'clean', 2)
+        ids = self.draw(self.rng if generator is None else generator, clean.shape[0], rir_ids)
+        wet, info = ops.reverb_rows(clean, self.bank, ids, lengths, prev)
+        info.update(rir_ids=ids, taps=self.bank.taps[ids], delays=self.bank.delays[ids])
+        return wet, info
+
+    def __call__(self, wav):
+        """Reverberate one waveform (numpy array or tensor, any shape: flattened)."""
+        if not torch.cuda.is_available():
+            raise RuntimeError('segan_pytorch_amd runs only on an MI355X (HIP) device; there is no '
+                               'CPU path')
+        if isinstance(wav, torch.Tensor):
+            wav = wav.detach().cpu().numpy()
+        x = torch.from_numpy(np.ascontiguousarray(np.asarray(wav, dtype=np.float32).reshape(1, -1)))
+        wet, _ = self.apply(x.cuda())
+        return wet[0].cpu().type(torch.FloatTensor)
 
 
 class ComposeAdditive(object):

@@ -290,13 +290,19 @@ class PCMShardLoader(object):
 
     def __init__(self, shard, batch_size, preemph, device, sampler=None, drop_last=False,
                  num_workers=2, additive=None, additive_prob=1.0, additive_seed=None,
-                 record_additive=False):
+                 record_additive=False, reverb=None, reverb_prob=1.0, reverb_seed=None,
+                 record_reverb=False):
         from torch.utils.data import RandomSampler
         if additive is not None and not 0.0 <= float(additive_prob) <= 1.0:
             raise ValueError('additive_prob must lie in 0 .. 1, got {}'.format(additive_prob))
         self.additive, self.additive_prob = additive, float(additive_prob)
         self.additive_rng = np.random.default_rng(additive_seed)
         self.additive_records = [] if record_additive else None
+        if reverb is not None and not 0.0 <= float(reverb_prob) <= 1.0:
+            raise ValueError('reverb_prob must lie in 0 .. 1, got {}'.format(reverb_prob))
+        self.reverb, self.reverb_prob = reverb, float(reverb_prob)
+        self.reverb_rng = np.random.default_rng(reverb_seed)      # its own stream of draws
+        self.reverb_records = [] if record_reverb else None
         self.shard = shard
         self.sampler = sampler if sampler is not None else RandomSampler(shard)
         self.preemph = float(preemph)
@@ -324,11 +330,51 @@ class PCMShardLoader(object):
         pcm_d = pcm.to(self.device, non_blocking=True)
         first_d = first.to(self.device, non_blocking=True)
         clean, noisy = ops.pcm16_prep(pcm_d, first_d, self.preemph)
+        wet = None
+        if self.reverb is not None:
+            names, wet = self._reverberate(names, pcm_d, first_d, noisy)
         if self.additive is not None:
-            names = self._add_noise(names, pcm_d, first_d, noisy)
+            names = self._add_noise(names, pcm_d, first_d, noisy, wet)
         return [names, clean, noisy, idx]
 
-    def _add_noise(self, names, pcm_d, first_d, noisy):
+    def _index_to_device(self, a):
+        # pinned staging and an asynchronous copy: a pageable copy would hold the host until the
+        # batch copy queued before it on this stream has finished
+        t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64))
+        if self.device.type == 'cuda':
+            t = t.pin_memory()
+        return t.to(self.device, non_blocking=True)
+
+    def _reverberate(self, names, pcm_d, first_d, noisy):
+        """On-the-fly reverberation (augment.Reverb), before any noise is
+        mixed: each item is selected with probability `reverb_prob` from the loader's own reverb
+        generator (the additive draws are the same with and without reverb).  A selected item's
+        wave is the fp32 min-max-normalised clean slice, convolved with a drawn RIR; the sample
+        preceding the slice takes part (zero where the slice starts its wav) and its reverberant
+        value is what the pre-emphasis of the row uses.  The noisy row becomes the pre-emphasised
+        reverberant wave — or, where the item is also selected for `additive`, `_add_noise` mixes
+        noise into the reverberant wave first.  '_reverb' is appended to the name; `clean` is
+        untouched.  Returns (names, (selected items, wet [n, T], wet prev [n]) or None)."""
+        from . import ops
+        B, T = noisy.shape
+        sel = np.nonzero(self.reverb_rng.random(B) < self.reverb_prob)[0]
+        if len(sel) == 0:
+            if self.reverb_records is not None:
+                self.reverb_records.append(None)
+            return names, None
+        wave, prev = ops.pcm16_wave(pcm_d, sel)
+        sel_d = self._index_to_device(sel)
+        prev = prev.masked_fill(first_d.index_select(0, sel_d) != 0, 0.0)   # nothing precedes a wav
+        wet, info = self.reverb.apply(wave, generator=self.reverb_rng, prev=prev)
+        ops.preemph_rows(wet, info['prev'], first_d, noisy, self.preemph, sel)
+        if self.reverb_records is not None:
+            info.update(index=sel, wave=wave, wave_prev=prev, wet=wet)
+            self.reverb_records.append(info)
+        chosen = set(sel.tolist())
+        return ([n + '_reverb' if i in chosen else n for i, n in enumerate(names)],
+                (sel, wet, info['prev']))
+
+    def _add_noise(self, names, pcm_d, first_d, noisy, wet=None):
         """On-the-fly additive noise (augment.Additive): each item is
         selected with probability `additive_prob`; a selected item's noisy row becomes clean +
         noise and its name gets '_additive' appended (WSEGAN's masked regression term applies to
@@ -339,7 +385,9 @@ class PCMShardLoader(object):
         (clean_prev + sf * noise[s-1]) followed by the slice's own anti-clipping divisions,
         rounded to fp32; when it does, y[0] = x[0].  The pre-emphasis is computed in double and
         rounded once, like the unaugmented rows.  Runs on the stream `_prep` runs on (the
-        loader's side stream), between the H2D copy and the consumer; `clean` is untouched."""
+        loader's side stream), between the H2D copy and the consumer; `clean` is untouched.
+        `wet`: what `_reverberate` returned; the wave of an item it selected is its reverberant
+        wave."""
         from . import ops
         B, T = noisy.shape
         sel = np.nonzero(self.additive_rng.random(B) < self.additive_prob)[0]
@@ -348,6 +396,15 @@ class PCMShardLoader(object):
                 self.additive_records.append(None)
             return names
         wave, prev = ops.pcm16_wave(pcm_d, sel)
+        if wet is not None:
+            # items that were reverberated: the level, sf and the divisions are taken on the
+            # reverberant wave, and the sample before the slice is the reverberant one
+            rsel, rwave, rprev = wet
+            both, ia, ir = np.intersect1d(sel, rsel, assume_unique=True, return_indices=True)
+            if len(both):
+                ix = self._index_to_device(np.stack([ia, ir]))
+                wave.index_copy_(0, ix[0], rwave.index_select(0, ix[1]))
+                prev.index_copy_(0, ix[0], rprev.index_select(0, ix[1]))
         mixed, info = self.additive.mix(wave, generator=self.additive_rng, prev=prev)
         ops.preemph_rows(mixed, info['prev'], first_d, noisy, self.preemph, sel)
         if self.additive_records is not None:

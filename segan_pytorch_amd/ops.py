@@ -1509,6 +1509,184 @@ def preemph_rows(x, prev, first, out, coef, index=None):
     return out
 
 
+# ---------------------------------------------------------------------------------
+# reverberation
+# ---------------------------------------------------------------------------------
+REVERB_P = 128           # SEGAN_REVERB_P (include/segan_hip.h): the partition; transforms are 2P
+REVERB_RIR = 1           # status bits of reverb_rows (SEGAN_REVERB_ST_*)
+REVERB_DELAY = 2
+_reverb_bases = {}
+_reverb_ws = {}
+
+
+def reverb_dims(rows, T, max_delay, max_taps=None):
+    """dict(P, blocks, frames, partitions, staging, spectrum, time, workspace) of
+    `segan_reverb_dims`: blocks of P samples per row, rows of the two transforms' products, and
+    the buffer sizes in floats."""
+    dims = (ctypes.c_int64 * 8)()
+    max_delay = _int_arg(max_delay, 'reverb_dims: max_delay', 0, 1 << 30)
+    taps = max_delay + 1 if max_taps is None else _int_arg(max_taps, 'reverb_dims: max_taps', 1, 1 << 30)
+    check(_lib.load().segan_reverb_dims(rows, T, max_delay, taps, dims), 'reverb_dims')
+    return dict(zip(('P', 'blocks', 'frames', 'partitions', 'staging', 'spectrum', 'time',
+                     'workspace'), (int(v) for v in dims)))
+
+
+def reverb_basis(device):
+    """(fwd [2P, 2P], inv [2P, P]): the shared DFT bases of the partitioned convolution, built once
+    per device."""
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise RuntimeError('reverb: segan_pytorch_amd runs only on an MI355X (HIP) device; there '
+                           'is no CPU path')
+    if device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    if device not in _reverb_bases:
+        with torch.cuda.device(device):
+            fwd = torch.empty((2 * REVERB_P, 2 * REVERB_P), device=device, dtype=torch.float32)
+            inv = torch.empty((2 * REVERB_P, REVERB_P), device=device, dtype=torch.float32)
+            check(_lib.load().segan_reverb_basis(_ptr(fwd), _ptr(inv), _stream()), 'reverb_basis')
+            torch.cuda.current_stream(device).synchronize()   # other streams may use it next
+        _reverb_bases[device] = (fwd, inv)
+    return _reverb_bases[device]
+
+
+def reverb_bank(taps):
+    """taps [n_parts, P] (fp32 CUDA: the RIRs zero-padded to whole partitions) -> H [n_parts, 2P],
+    the packed spectra of the partitions zero-padded to 2P."""
+    _chk(taps, 'taps', 2)
+    if taps.shape[1] != REVERB_P or taps.shape[0] == 0:
+        raise ValueError('reverb_bank: taps must be [n_parts, {}], got {}'.format(
+            REVERB_P, tuple(taps.shape)))
+    fwd, _ = reverb_basis(taps.device)
+    H = torch.empty((taps.shape[0], 2 * REVERB_P), device=taps.device, dtype=torch.float32)
+    check(_lib.load().segan_reverb_bank(_ptr(taps), taps.shape[0], _ptr(fwd), _ptr(H), _stream()),
+          'reverb_bank')
+    return H
+
+
+class ReverbBankData(object):
+    """What `reverb_rows` needs of a bank on one device: H [n_parts, 2P] (`reverb_bank`), table
+    int32 [n_rirs, 4] = (first partition, partitions, taps, delay) on the device, and the largest
+    delay (a host integer: it sizes the buffers)."""
+
+    def __init__(self, H, table, max_delay):
+        _chk(H, 'H', 2)
+        if not (isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.int32 and
+                table.dim() == 2 and table.shape[1] == 4 and table.is_contiguous() and
+                table.shape[0] > 0 and table.device == H.device):
+            raise TypeError('ReverbBankData: table must be a contiguous CUDA int32 [n_rirs, 4] on '
+                            "H's device")
+        if H.shape[1] != 2 * REVERB_P or H.shape[0] == 0:
+            raise ValueError('ReverbBankData: H must be [n_parts, {}]'.format(2 * REVERB_P))
+        self.H, self.table = H, table
+        self.max_delay = _int_arg(max_delay, 'ReverbBankData: max_delay', 0, 1 << 30)
+
+
+def _reverb_args(x, bank, rir_ids, lengths, prev):
+    _chk(x, 'x', 2)
+    rows, T = x.shape
+    if rows == 0 or T == 0:
+        raise ValueError('reverb_rows: empty input {}'.format(tuple(x.shape)))
+    if not isinstance(bank, (ReverbBankData, torch.Tensor)) and callable(getattr(bank, 'data', None)):
+        bank = bank.data(x.device)      # an augment.RIRBank
+    if not isinstance(bank, ReverbBankData):
+        raise TypeError('reverb_rows: bank must be an augment.RIRBank or a ReverbBankData')
+    if bank.H.device != x.device:
+        raise ValueError('reverb_rows: tensors on different devices')
+    if isinstance(rir_ids, torch.Tensor) and rir_ids.is_cuda:
+        ids = rir_ids
+        if ids.dtype != torch.int32 or ids.numel() != rows or not ids.is_contiguous():
+            raise ValueError('reverb_rows: device rir_ids must be contiguous int32 [{}]'.format(rows))
+    else:
+        ids = torch.as_tensor(rir_ids).detach().cpu().reshape(-1)
+        if ids.numel() != rows or ids.dtype.is_floating_point or ids.dtype == torch.bool:
+            raise ValueError('reverb_rows: rir_ids must hold {} integers, got {}'.format(
+                rows, rir_ids))
+        ids = ids.to(torch.int64)
+        if int(ids.min()) < -(1 << 31) or int(ids.max()) >= (1 << 31):
+            raise ValueError('reverb_rows: rir_ids do not fit 32 bits')
+        # pinned staging, asynchronous copy (see additive_mix)
+        ids = ids.to(torch.int32).pin_memory().to(x.device, non_blocking=True)
+    lens = None if lengths is None else _row_lengths('reverb_rows', lengths, rows, T, x.device)
+    if prev is not None:
+        _chk(prev, 'prev', 1)
+        if prev.numel() != rows:
+            raise ValueError('reverb_rows: prev must hold {} values'.format(rows))
+    return bank, ids, lens
+
+
+def _reverb_workspace(floats, device):
+    """The chain's workspace (120 MB at [300, 16384]), kept per (device, stream) and grown on
+    demand: calls on one stream run in order, so they can share it; another stream gets its own.
+    The buffer is held for the life of the process (it only grows and is never released; an entry
+    outlives its stream) — one per stream that ever reverberated, the loader's side stream in
+    training."""
+    key = (device, _stream().value)
+    ws = _reverb_ws.get(key)
+    if ws is None or ws.numel() < floats:
+        ws = _reverb_ws[key] = torch.empty(floats, device=device, dtype=torch.float32)
+    return ws
+
+
+def reverb_rows(x, bank, rir_ids, lengths=None, prev=None):
+    """x [rows, T] (fp32 CUDA) convolved row by row with the room impulse responses `rir_ids`
+    (host integers or a CUDA int32 tensor, [rows]) of `bank` (an `augment.RIRBank`, or its
+    `data(device)`): y[n] = sum_k h[k] x[n + d - k] with d the RIR's direct path (DESIGN.md section
+    14), x[-1] = prev (optional fp32 CUDA [rows]), zero outside the row's `lengths`.  Returns
+    (y [rows, T], info): info['prev'] = y[-1] (fp32 [rows]; what a pre-emphasis that follows
+    needs), info['status'] int32 [rows]: REVERB_RIR (the id is not in the bank) | REVERB_DELAY;
+    a flagged row is returned unchanged.  No device-to-host copy."""
+    bank, ids, lens = _reverb_args(x, bank, rir_ids, lengths, prev)
+    rows, T = x.shape
+    fwd, inv = reverb_basis(x.device)
+    dims = reverb_dims(rows, T, bank.max_delay)
+    ws = _reverb_workspace(dims['workspace'], x.device)
+    y = torch.empty_like(x)
+    prev_out = torch.empty(rows, device=x.device, dtype=torch.float32)
+    status = torch.empty(rows, device=x.device, dtype=torch.int32)
+    check(_lib.load().segan_reverb_rows(
+        _ptr(x), _ptr(lens), _ptr(prev), _ptr(bank.H), bank.H.shape[0], _ptr(ids),
+        _ptr(bank.table), bank.table.shape[0], _ptr(fwd), _ptr(inv), rows, T, bank.max_delay,
+        _ptr(ws), ws.numel(), _ptr(y), _ptr(prev_out), _ptr(status), _stream()), 'reverb_rows')
+    return y, dict(prev=prev_out, status=status)
+
+
+def reverb_stages(x, bank, rir_ids, lengths=None, prev=None, X=None, yt=None):
+    """`reverb_rows` stage by stage through the library's separate entry points (tests, timing):
+    returns dict(xs, X, Y, yt, y, prev, status, dims).  X / yt given: the delay line / the output
+    stage run on those instead of on the products of the stages before."""
+    bank, ids, lens = _reverb_args(x, bank, rir_ids, lengths, prev)
+    rows, T = x.shape
+    lib = _lib.load()
+    fwd, inv = reverb_basis(x.device)
+    dims = reverb_dims(rows, T, bank.max_delay)
+    NB, M, P = dims['blocks'], dims['frames'], REVERB_P
+    dev = x.device
+    xs = torch.empty(dims['staging'], device=dev, dtype=torch.float32)
+    check(lib.segan_reverb_stage(_ptr(x), _ptr(lens), _ptr(prev), _ptr(xs), rows, T, NB, M,
+                                 _stream()), 'reverb_stage')
+    if X is None:
+        X = torch.empty((M, 2 * P), device=dev, dtype=torch.float32)
+        check(lib.segan_reverb_forward(_ptr(xs), _ptr(fwd), _ptr(X), M, _stream()),
+              'reverb_forward')
+    Y = torch.empty((M, 2 * P), device=dev, dtype=torch.float32)
+    check(lib.segan_reverb_fdl(_ptr(X), _ptr(bank.H), bank.H.shape[0], _ptr(ids), _ptr(bank.table),
+                               bank.table.shape[0], _ptr(Y), rows, T, NB, M, _stream()),
+          'reverb_fdl')
+    if yt is None:
+        yt = torch.empty((M, P), device=dev, dtype=torch.float32)
+        check(lib.segan_reverb_inverse(_ptr(Y), _ptr(inv), _ptr(yt), M, _stream()),
+              'reverb_inverse')
+    y = torch.empty_like(x)
+    prev_out = torch.empty(rows, device=dev, dtype=torch.float32)
+    status = torch.empty(rows, device=dev, dtype=torch.int32)
+    check(lib.segan_reverb_finish(_ptr(yt), _ptr(x), _ptr(lens), _ptr(prev), bank.H.shape[0],
+                                  _ptr(ids), _ptr(bank.table), bank.table.shape[0], _ptr(y),
+                                  _ptr(prev_out), _ptr(status), rows, T, NB, M, _stream()),
+          'reverb_finish')
+    return dict(xs=xs, X=X, Y=Y, yt=yt, y=y, prev=prev_out, status=status, dims=dims)
+
+
 def rmsprop_step(p, g, sq, lr, alpha, eps):
     check(_lib.load().segan_rmsprop_step(_ptr(p), _ptr(g), _ptr(sq), lr, alpha, eps, p.numel(),
                                          _stream()), 'rmsprop_step')

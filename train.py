@@ -9,7 +9,10 @@ same defaults, same `train.opts` dump) driving the HIP engine in `segan_pytorch_
 Additions over the reference: `--synthetic N` trains on N fixed-seed synthetic chunk
 pairs (no dataset needed), `--pcm_shard PREFIX` trains from a pre-sliced int16 shard whose
 batches are normalised / pre-emphasised on the GPU (with `--additive_noises DIR` noise is mixed
-into them on the fly at `--additive_snrs` dB, the reference's Additive), and under
+into them on the fly at `--additive_snrs` dB, the reference's Additive; with `--reverb_rirs DIR`
+each selected clean slice is first convolved on the GPU with a room impulse response drawn from
+DIR's wavs: `--reverb_prob` is the share of items selected, `--reverb_max_taps` cuts the
+responses, `--reverb_resample` converts responses that are not 16 kHz), and under
 torch.distributed.run every
 rank trains on its shard of each epoch with RCCL gradient averaging.
 """
@@ -157,6 +160,20 @@ FLAGS = [
                                  help='with --additive_noises: convert noise wavs that are not '
                                       '16 kHz (the DEMAND noises are 48 kHz) to 16 kHz on the GPU '
                                       'when they are read; without it their rate is ignored')),
+    ('--reverb_rirs', dict(type=str, default=None,
+                           help='with --pcm_shard: directory of room impulse response wavs; the '
+                                'clean wave of each selected item is convolved on the GPU with one '
+                                'of them (direct path aligned with the dry target, gain 1) before '
+                                'any noise is mixed, and \'_reverb\' is appended to its utterance '
+                                'name')),
+    ('--reverb_prob', dict(type=float, default=1.0,
+                           help='probability that an item is reverberated')),
+    ('--reverb_max_taps', dict(type=int, default=16384,
+                               help='impulse responses are cut to this many taps')),
+    ('--reverb_resample', dict(action='store_true', default=False,
+                               help='with --reverb_rirs: convert responses that are not 16 kHz to '
+                                    '16 kHz on the GPU when they are read; without it their rate '
+                                    'is ignored')),
 ]
 
 
@@ -181,6 +198,27 @@ def check_additive_flags(opts):
     return True
 
 
+def check_reverb_flags(opts):
+    """The --reverb_* flags go together with --pcm_shard; anything else exits with a message."""
+    rirs = getattr(opts, 'reverb_rirs', None)
+    prob = getattr(opts, 'reverb_prob', 1.0)
+    max_taps = getattr(opts, 'reverb_max_taps', 16384)
+    if rirs is None:
+        if prob != 1.0 or max_taps != 16384:
+            raise SystemExit('--reverb_prob / --reverb_max_taps need --reverb_rirs DIR')
+        if getattr(opts, 'reverb_resample', False):
+            raise SystemExit('--reverb_resample needs --reverb_rirs DIR')
+        return False
+    if getattr(opts, 'pcm_shard', None) is None or getattr(opts, 'synthetic', 0) > 0:
+        raise SystemExit('--reverb_rirs reverberates the batches of a pcm16 shard on the GPU: it '
+                         'is valid only together with --pcm_shard PREFIX')
+    if not 0.0 <= prob <= 1.0:
+        raise SystemExit('--reverb_prob must lie in 0 .. 1, got {}'.format(prob))
+    if max_taps < 1:
+        raise SystemExit('--reverb_max_taps must be positive, got {}'.format(max_taps))
+    return True
+
+
 def build_parser():
     p = argparse.ArgumentParser(description=__doc__,
                                 formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -191,6 +229,7 @@ def build_parser():
 
 def main(opts):
     use_additive = check_additive_flags(opts)
+    use_reverb = check_reverb_flags(opts)
     if getattr(opts, 'sync_bn', False):
         os.environ['SEGAN_SYNC_BN'] = '1'
     rank, world, local = sdist.init_from_env()
@@ -256,10 +295,20 @@ def main(opts):
             from segan_pytorch_amd.augment import Additive
             additive = Additive(opts.additive_noises, opts.additive_snrs,
                                 target_rate=16000 if opts.additive_resample else None)
+        reverb = None
+        if use_reverb:
+            from segan_pytorch_amd.augment import Reverb
+            reverb = Reverb(opts.reverb_rirs, max_taps=opts.reverb_max_taps,
+                            target_rate=16000 if opts.reverb_resample else None)
         dloader = PCMShardLoader(dset, opts.batch_size, opts.preemph, device, sampler=sampler,
                                  drop_last=(world > 1), num_workers=max(1, min(2, opts.num_workers)),
                                  additive=additive, additive_prob=opts.additive_prob,
-                                 additive_seed=opts.seed + rank)
+                                 additive_seed=opts.seed + rank, reverb=reverb,
+                                 reverb_prob=opts.reverb_prob,
+                                 # derived from seed + rank like the additive stream, but another
+                                 # stream: the same integer would make both selections draw the
+                                 # same uniforms
+                                 reverb_seed=[opts.seed + rank, 1])
     else:
         dloader = DataLoader(dset, batch_size=opts.batch_size, shuffle=(sampler is None),
                              sampler=sampler, num_workers=workers, pin_memory=pin,
