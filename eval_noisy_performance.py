@@ -2,7 +2,7 @@
 the clean wavs of the same names, on the MI355X: the reference's eval_noisy_performance.py.
 
     python eval_noisy_performance.py --test_wavs DIR --clean_wavs DIR --logfile FILE [--stoi]
-                                     [--estoi] [--fwsegsnr] [--cd] [--sisdr] [--resample]
+                                     [--estoi] [--fwsegsnr] [--cd] [--sisdr] [--sdr] [--resample]
 
 16 kHz wavs only (int16 files are scaled by 1/32768, float files used as they are), unless
 --resample converts files of other rates to 16 kHz on the GPU first (int16 files to int16, float
@@ -13,7 +13,9 @@ mean STOI line; --estoi does the same with an ESTOI column (quality.estoi, exten
 STOI's when both are given.  --fwsegsnr, --cd and --sisdr add, in that order after them, the
 columns FWSEGSNR (quality.fwsegsnr, frequency-weighted segmental SNR in dB), CD
 (quality.cepstral_distance, LPC cepstrum distance) and SISDR (quality.si_sdr, scale-invariant SDR
-in dB) with their final mean lines; none of the three needs pesqmain."""
+in dB) with their final mean lines; none of the three needs pesqmain.  --sdr adds, after them, the
+column SDR (quality.sdr, the BSS-eval signal-to-distortion ratio in dB with a 512-tap distortion
+filter) and its mean line."""
 import argparse
 import glob
 import os
@@ -54,7 +56,7 @@ def read_wav(path, opts=None):
 # the optional columns in their order: (column, flag, function of segan_pytorch_amd.quality)
 EXTRA = (('STOI', 'stoi', 'stoi'), ('ESTOI', 'estoi', 'estoi'),
          ('FWSEGSNR', 'fwsegsnr', 'fwsegsnr'), ('CD', 'cd', 'cepstral_distance'),
-         ('SISDR', 'sisdr', 'si_sdr'))
+         ('SISDR', 'sisdr', 'si_sdr'), ('SDR', 'sdr', 'sdr'))
 
 
 def header_line(opts):
@@ -71,7 +73,7 @@ def main(opts):
     extra = [(name, getattr(quality, fn)) for name, flag, fn in EXTRA if getattr(opts, flag)]
     noisy_wavs = sorted(glob.glob(os.path.join(opts.test_wavs, '*.wav')))
     metrics = {'csig': [], 'cbak': [], 'covl': [], 'STOI': [], 'ESTOI': [], 'FWSEGSNR': [],
-               'CD': [], 'SISDR': []}
+               'CD': [], 'SISDR': [], 'SDR': []}
     timings = []
     with open(opts.logfile, 'w') as out_log:
         out_log.write(header_line(opts) + '\n')
@@ -125,6 +127,9 @@ def build_parser():
                         help='also compute CD (LPC cepstrum distance)')
     parser.add_argument('--sisdr', action='store_true', default=False,
                         help='also compute SI-SDR (scale-invariant signal-to-distortion ratio, dB)')
+    parser.add_argument('--sdr', action='store_true', default=False,
+                        help='also compute SDR (BSS-eval signal-to-distortion ratio with a '
+                             '512-tap distortion filter, dB)')
     parser.add_argument('--resample', action='store_true', default=False,
                         help='convert wavs that are not 16 kHz to 16 kHz on the GPU instead of '
                              'refusing them')

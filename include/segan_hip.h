@@ -469,6 +469,35 @@ int segan_cepdist(const float* ref, const float* deg, const int* lengths, int ro
                   int srate, double* frames_out, void* stream);
 int segan_sisdr(const float* ref, const float* deg, const int* lengths, int rows, int T,
                 double* row_out, double* ws, void* stream);
+/* BSS-eval SDR (the SDR of bss_eval_sources with a distortion filter of `taps` <= 512 taps), fp64
+ * on fp32 rows ref / deg [rows][T], row r restricted to its first lengths[r] = L samples (device
+ * int[rows], clamped to 0 .. T; NULL: all T); DESIGN.md section 15.  With s, x the row, zero
+ * outside [0, L), and n = taps:
+ *   r[k] = sum_t s[t] s[t+k], d[k] = sum_t s[t] x[t+k], k < n: exact products, added per span of
+ *     SEGAN_SDR_SPAN samples of t in ascending order, then the spans in ascending order;
+ *   Toeplitz(r) c = d by the Levinson recursion; at order m with prediction error E_m <=
+ *     2^-40 r[0] the recursion stops, c[k] = 0 for k >= m, and m is the order reached (else n);
+ *   st[t] = sum_k c[k] s[t-k] (k ascending), t < L + n - 1; St = sum st^2, Ee = sum (x - st)^2,
+ *     sample by sample;
+ *   row_out[rows] = 10 log10(St / Ee) dB; NaN where L == 0, r[0] == 0 or St == Ee == 0; else +inf
+ *     where Ee == 0 (deg == g ref, g a power of two: c = g delta exactly), -inf where St == 0.
+ * No atomics, every sum in an order fixed by the sample index: a row's bits depend neither on T,
+ * nor on the other rows, nor on the samples past its length.
+ *   segan_sdr_dims (host only): out[3] = {SEGAN_SDR_SPAN, ceil(T / SEGAN_SDR_SPAN), the doubles of
+ *     segan_sdr's workspace `ws`}.
+ *   segan_sdr: stages_out (may be NULL) [rows][3 taps + 3]: r[taps], d[taps], c[taps], the order
+ *     reached, St, Ee of each row.
+ *   segan_toeplitz_solve: the solver on its own, r / d / c_out [rows][n] fp64, n <= 512,
+ *     order_out int[rows]; same guard.
+ * rows in 1 .. 65535, T > 0, taps in 1 .. SEGAN_SDR_MAX_TAPS, checked before any launch.  Added
+ * without a change of SEGAN_ABI_VERSION: the exports are purely additive. */
+#define SEGAN_SDR_SPAN 4096
+#define SEGAN_SDR_MAX_TAPS 512
+int segan_sdr_dims(int rows, int T, int taps, long long* out);
+int segan_sdr(const float* ref, const float* deg, const int* lengths, int rows, int T, int taps,
+              double* row_out, double* stages_out, double* ws, void* stream);
+int segan_toeplitz_solve(const double* r, const double* d, int rows, int n, double* c_out,
+                         int* order_out, void* stream);
 
 /* ---- on-the-fly additive noise (the reference's Additive, utils.py:43-297)
  * fp64 arithmetic on fp32 rows x / clean [rows][T], row r restricted to its first lengths[r]

@@ -9,6 +9,10 @@ utterance like eval_noisy_performance.py, with a device synchronise; prints one 
         # quality.fwsegsnr / cepstral_distance / si_sdr over the set padded to its longest
         # utterance with `lengths`, beside quality.stoi's batched call; the JSON line also goes to
         # --out (profiles/measures_bench.json)
+    python scripts/bench_quality.py --sdr        # instead: ONE batched call of quality.sdr (BSS-eval
+        # SDR, 512 taps) over the same set, and the numpy oracle scripts/sdr_oracle.py on
+        # --sdr-cpu of its utterances; the JSON line also goes to --sdr-out
+        # (profiles/sdr_bench.json)
 """
 import argparse
 import json
@@ -42,8 +46,19 @@ def main():
                     help='also time the batched fwSNRseg + CD + SI-SDR call (and STOI\'s)')
     ap.add_argument('--batch-reps', type=int, default=5)
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'measures_bench.json'))
+    ap.add_argument('--sdr', action='store_true',
+                    help='time the batched BSS-eval SDR call and its numpy oracle instead')
+    ap.add_argument('--sdr-cpu', type=int, default=3)
+    ap.add_argument('--sdr-out', default=os.path.join(ROOT, 'profiles', 'sdr_bench.json'))
     args = ap.parse_args()
     utts = utterances()
+    if args.sdr:
+        import torch
+        out = batched_sdr(torch, utts, args.batch_reps, args.sdr_cpu)
+        with open(args.sdr_out, 'w') as f:
+            f.write(json.dumps(out) + '\n')
+        print(json.dumps(out))
+        return
     if args.cpu_ref:
         sys.path.insert(0, os.path.join(ROOT, 'oracle'))
         import ref_harness
@@ -114,6 +129,39 @@ def batched_measures(torch, utts, reps):
         out[k + '_nonfinite_rows'] = int((~torch.isfinite(v)).sum())
     out['stoi_batched_seconds'] = timed(lambda: quality.stoi(ref, deg, lengths=lengths))[0]
     return out
+
+
+def batched_sdr(torch, utts, reps, ncpu):
+    """Seconds of one batched quality.sdr call over the whole set (after one warm-up call, mean of
+    `reps`, up to a device synchronise), the oracle's seconds per utterance on the first `ncpu`
+    utterances, and the largest difference between the two on those."""
+    sys.path.insert(0, os.path.join(ROOT, 'scripts'))
+    import sdr_oracle
+    from segan_pytorch_amd import ops, quality
+    lengths = [len(c) for c, _ in utts]
+    ref = torch.zeros(len(utts), max(lengths))
+    deg = torch.zeros(len(utts), max(lengths))
+    for i, (c, d) in enumerate(utts):
+        ref[i, :len(c)] = torch.from_numpy(c)
+        deg[i, :len(d)] = torch.from_numpy(d)
+    ref, deg = ref.cuda(), deg.cuda()
+    v = quality.sdr(ref, deg, lengths=lengths)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        v = quality.sdr(ref, deg, lengths=lengths)
+    torch.cuda.synchronize()
+    dt = (time.perf_counter() - t0) / reps
+    t0 = time.perf_counter()
+    want = [sdr_oracle.sdr(c, d) for c, d in utts[:ncpu]]
+    cpu = (time.perf_counter() - t0) / max(ncpu, 1)
+    got = v[:ncpu].cpu().tolist()
+    return {'leg': 'mi355x', 'measure': 'sdr', 'taps': ops.SDR_TAPS, 'utts': len(utts),
+            'mean_audio_s': float(np.mean(lengths)) / 16000, 'batched_seconds': dt,
+            'batched_utts_per_s': len(utts) / dt, 'mean_sdr': float(v[torch.isfinite(v)].mean()),
+            'sdr_nonfinite_rows': int((~torch.isfinite(v)).sum()),
+            'oracle_cpu_utts': ncpu, 'oracle_cpu_s_per_utt': cpu,
+            'max_abs_diff_db_vs_oracle': max([abs(a - b) for a, b in zip(got, want)] or [0.0])}
 
 
 if __name__ == '__main__':

@@ -103,6 +103,9 @@ SIGNATURES = {
     'segan_fwsegsnr': (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
     'segan_cepdist': (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P]),
     'segan_sisdr': (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P]),
+    'segan_sdr_dims': (c_int, [c_int, c_int, c_int, POINTER(c_int64)]),
+    'segan_sdr': (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P]),
+    'segan_toeplitz_solve': (c_int, [_P, _P, c_int, c_int, _P, _P, _P]),
     'segan_asl_p56': (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     'segan_additive_mix': (c_int, [_P, _P, _P, c_int64, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P]),
     'segan_resample_plan': (c_int, [c_int, c_int, c_int, c_double, POINTER(c_int), POINTER(c_int), _P, c_int]),

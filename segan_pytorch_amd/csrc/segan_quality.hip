@@ -348,21 +348,6 @@ __device__ __forceinline__ int row_frames(int L, int win, int skip) {   // segan
   return nf > 0 ? nf : 0;
 }
 
-// the sums of N values over a 256-thread workgroup in a fixed order (butterfly, then the four
-// waves in turn); the result is in every thread
-template <int N>
-__device__ __forceinline__ void block_sum_fixed(double (&v)[N], double (*sh)[N]) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int j = 0; j < N; ++j) {
-    v[j] = segan_wave_sum(v[j]);
-    if (lane == 0) sh[wave][j] = v[j];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < N; ++j) v[j] = ((sh[0][j] + sh[1][j]) + sh[2][j]) + sh[3][j];
-}
-
 // fwSNRseg.  WSS's layout: one 256-thread workgroup per (frame, row), the windowed pair and the
 // twiddles in LDS, a direct fp64 DFT, here of all nfft/2 bins (at most QF_BINS per thread, kept
 // in registers) and to the magnitude.  The block sum of the magnitudes normalises them into the

@@ -1,4 +1,4 @@
-// What the fp64 signal files (audio, quality, STOI, additive, resample) share: each piece here has
+// What the fp64 signal files (audio, quality, BSS-eval, STOI, additive, resample) share: each piece here has
 // more than one user.  The Hann windows are NOT here: quality, STOI and SSNR each round theirs
 // the way their own oracle does.
 #pragma once
@@ -13,6 +13,21 @@ __device__ __forceinline__ double segan_wave_sum(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+
+// the sums of N values over a 256-thread workgroup in a fixed order (butterfly, then the four
+// waves in turn); the result is in every thread
+template <int N>
+__device__ __forceinline__ void block_sum_fixed(double (&v)[N], double (*sh)[N]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    v[j] = segan_wave_sum(v[j]);
+    if (lane == 0) sh[wave][j] = v[j];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < N; ++j) v[j] = ((sh[0][j] + sh[1][j]) + sh[2][j]) + sh[3][j];
 }
 
 // the row's valid samples: lengths[r] clamped to [0, T] (all T without lengths)

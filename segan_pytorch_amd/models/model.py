@@ -424,7 +424,8 @@ class SEGAN(Model):
         --eval_stoi) a key 'stoi' (quality.stoi, 16 kHz) is added, computed on the same signals;
         with `opts.eval_estoi` (train.py --eval_estoi) a key 'estoi' (quality.estoi) likewise,
         and with `opts.eval_fwsegsnr` / `eval_cd` / `eval_sisdr` the keys 'fwsegsnr', 'cd',
-        'sisdr' (quality.fwsegsnr, quality.cepstral_distance, quality.si_sdr).
+        'sisdr' (quality.fwsegsnr, quality.cepstral_distance, quality.si_sdr), and with
+        `opts.eval_sdr` the key 'sdr' (quality.sdr, BSS-eval SDR with a 512-tap filter).
         De-emphasis runs along time (the reference applies it along axis 0 of the [B, T] batch,
         model.py:474-477)."""
         from .. import ops, quality
@@ -434,7 +435,7 @@ class SEGAN(Model):
         with_estoi = bool(getattr(opts, 'eval_estoi', False))
         more = [(k, fn) for k, fn in (('fwsegsnr', quality.fwsegsnr),
                                       ('cd', quality.cepstral_distance),
-                                      ('sisdr', quality.si_sdr))
+                                      ('sisdr', quality.si_sdr), ('sdr', quality.sdr))
                 if bool(getattr(opts, 'eval_' + k, False))]
         keys = ('ssnr', 'snr', 'pesq', 'csig', 'cbak', 'covl', 'wss', 'llr') + (
             ('stoi',) if with_stoi else ()) + (('estoi',) if with_estoi else ()) + tuple(

@@ -1253,6 +1253,79 @@ def si_sdr(ref, deg, lengths=None):
     return out
 
 
+SDR_TAPS = 512           # SEGAN_SDR_MAX_TAPS (include/segan_hip.h): the longest distortion filter
+SDR_SPAN = 4096          # SEGAN_SDR_SPAN: samples per partial sum
+
+
+def sdr_stages(ref, deg, lengths=None, taps=SDR_TAPS):
+    """Every stage of `sdr` (BSS-eval SDR) of each row of ref / deg
+    [rows, T] (fp32 CUDA tensors) on the device, as a dict of fp64 tensors: 'r', 'd' [rows, taps]
+    (the lagged auto- and cross-correlations), 'c' [rows, taps] (the distortion filter, zero from
+    the order reached on), 'order' [rows] (int64: taps unless the recursion's guard stopped it),
+    'target_energy', 'error_energy', 'sdr' [rows].  Row r is ref[r, :lengths[r]] (host integers
+    0 .. T; all T without `lengths`).  No device-to-host copy."""
+    _chk(ref, 'ref', 2)
+    _chk(deg, 'deg', 2)
+    if ref.shape != deg.shape:
+        raise ValueError('sdr: shapes differ {} vs {}'.format(tuple(ref.shape), tuple(deg.shape)))
+    rows, T = ref.shape
+    if not 1 <= rows <= 65535 or T < 1:
+        raise ValueError('sdr: 1 .. 65535 rows of at least one sample, got {}'.format(
+            tuple(ref.shape)))
+    n = _int_arg(taps, 'sdr: taps', 1, SDR_TAPS)
+    lens = None if lengths is None else _row_lengths('sdr', lengths, rows, T, ref.device)
+    lib = _lib.load()
+    dims = (ctypes.c_int64 * 3)()
+    check(lib.segan_sdr_dims(rows, T, n, dims), 'sdr')
+    ws = _stream_scratch(8 * dims[2], ref.device)
+    out = torch.empty(rows, device=ref.device, dtype=torch.float64)
+    stages = torch.empty((rows, 3 * n + 3), device=ref.device, dtype=torch.float64)
+    check(lib.segan_sdr(_ptr(ref), _ptr(deg), _ptr(lens), rows, T, n, _ptr(out), _ptr(stages),
+                        _ptr(ws), _stream()), 'sdr')
+    return {'r': stages[:, :n], 'd': stages[:, n:2 * n], 'c': stages[:, 2 * n:3 * n],
+            'order': stages[:, 3 * n].to(torch.int64), 'target_energy': stages[:, 3 * n + 1],
+            'error_energy': stages[:, 3 * n + 2], 'sdr': out}
+
+
+def sdr(ref, deg, lengths=None, taps=SDR_TAPS):
+    """BSS-eval signal-to-distortion ratio in dB (the SDR of bss_eval_sources) of each row of
+    ref / deg [rows, T] on the device: deg is projected onto the span of ref and its first
+    taps - 1 delays (taps in 1 .. 512), 10 log10 of the projection's energy over the rest's; fp64
+    [rows].  NaN for a row of no samples, a clean row without energy or a processed row of zeros;
+    +inf where the processed row is the clean one times a power of two.  Fixed summation order: a
+    batched row equals its own call bit for bit.  `lengths` as in `sdr_stages`."""
+    return sdr_stages(ref, deg, lengths, taps)['sdr']
+
+
+def toeplitz_solve(r, d):
+    """Solves Toeplitz(r) c = d for each row of r / d ([rows, n] or [n] fp64 CUDA tensors, n <=
+    512; r the first column of a symmetric positive definite Toeplitz matrix) by the Levinson
+    recursion on the device.  Returns (c fp64 like r, order int32 [rows]): at order m with
+    prediction error E_m <= 2^-40 r[0] the recursion stops, c[m:] is zero and order is m; else
+    order is n."""
+    for t, name in ((r, 'r'), (d, 'd')):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError('{} must be a tensor, got {}'.format(name, type(t)))
+        if not t.is_cuda:
+            raise RuntimeError('{} is on {}: segan_pytorch_amd runs only on an MI355X (HIP) device; '
+                               'there is no CPU path'.format(name, t.device))
+        if t.dtype != torch.float64:
+            raise TypeError('{} must be float64, got {}'.format(name, t.dtype))
+    if r.shape != d.shape or r.dim() not in (1, 2):
+        raise ValueError('toeplitz_solve: r {} and d {} must be [rows, n] or [n] of one shape'
+                         .format(tuple(r.shape), tuple(d.shape)))
+    r2, d2 = r.reshape(-1, r.shape[-1]).contiguous(), d.reshape(-1, r.shape[-1]).contiguous()
+    rows, n = r2.shape
+    if not 1 <= rows <= 65535 or not 1 <= n <= SDR_TAPS:
+        raise ValueError('toeplitz_solve: 1 .. 65535 rows of 1 .. {} values, got {}'.format(
+            SDR_TAPS, tuple(r.shape)))
+    c = torch.empty_like(r2)
+    order = torch.empty(rows, device=r.device, dtype=torch.int32)
+    check(_lib.load().segan_toeplitz_solve(_ptr(r2), _ptr(d2), rows, n, _ptr(c), _ptr(order),
+                                           _stream()), 'toeplitz_solve')
+    return c.reshape(r.shape), order
+
+
 ASL_THRESHOLDS = 15      # nbits - 1 thresholds 2^-15 .. 2^-1 (nbits = 16)
 ADDITIVE_CAP = 1         # status bits of asl_p56 / additive_mix (include/segan_hip.h)
 ADDITIVE_PN0 = 2

@@ -235,3 +235,14 @@ def si_sdr(ref, deg, lengths=None):
     `lengths` as for `stoi`): fp64 tensor [rows].  NaN for a clean signal without energy once its
     mean is removed, +inf where the processed signal is an exact scaled, shifted copy."""
     return ops.si_sdr(*_same_shape_rows('si_sdr', ref, deg), lengths)
+
+
+def sdr(ref, deg, lengths=None, taps=ops.SDR_TAPS):
+    """BSS-eval signal-to-distortion ratio in dB (the SDR of bss_eval_sources, DESIGN.md section
+    15) of each row of ref / deg (shapes as for `stoi`; `lengths`: per-row sample counts 0 .. T):
+    the processed signal projected onto the clean one and its first taps - 1 delays (taps in
+    1 .. 512), the projection's energy over the rest's; fp64 tensor [rows].  Unlike `si_sdr` it
+    does not punish a short filter or delay left in the processed signal.  NaN for a row without
+    samples, a clean signal without energy or a processed signal of zeros; +inf where the
+    processed signal is the clean one times a power of two."""
+    return ops.sdr(*_same_shape_rows('sdr', ref, deg), lengths, taps)

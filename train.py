@@ -76,6 +76,9 @@ FLAGS = [
                        help='the evaluation also reports CD (LPC cepstrum distance)')),
     ('--eval_sisdr', dict(action='store_true', default=False,
                           help='the evaluation also reports SI-SDR (scale-invariant SDR)')),
+    ('--eval_sdr', dict(action='store_true', default=False,
+                        help='the evaluation also reports SDR (BSS-eval signal-to-distortion '
+                             'ratio with a 512-tap distortion filter)')),
     ('--slice_workers', dict(type=int, default=1)),
     ('--num_workers', dict(type=int, default=1)),
     ('--no-cuda', dict(action='store_true', default=False)),
