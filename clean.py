@@ -9,7 +9,9 @@ the HIP path.
 Files are taken as 16 kHz whatever their header says, as in the reference, unless --resample is
 given: a file of another rate is then converted to 16 kHz int16 on the GPU first (the reference
 leans on librosa.load(path, 16000) or an offline sox pass), and with --keep_rate the enhanced
-signal is converted back and written at the file's own rate and length.
+signal is converted back and written at the file's own rate and length.  --srmr prints the SRMR
+(quality.srmr, the speech-to-reverberation modulation energy ratio, which needs no clean signal)
+of each enhanced signal at 16 kHz and the mean over the files.
 """
 import argparse
 import glob
@@ -53,6 +55,9 @@ def build_parser():
                         '--resample_beta 5.0 is scipy\'s default)'.format(RESAMPLE_ZEROS))
     p.add_argument('--resample_beta', type=float, default=argparse.SUPPRESS,
                    help='Kaiser beta of the conversion filter (default {})'.format(RESAMPLE_BETA))
+    p.add_argument('--srmr', action='store_true', default=argparse.SUPPRESS,
+                   help='print the SRMR (speech-to-reverberation modulation energy ratio) of each '
+                        'enhanced signal at 16 kHz, and the mean')
     return p
 
 
@@ -86,6 +91,7 @@ def main(opts):
     else:
         twavs = opts.test_files
     print('Cleaning {} wavs'.format(len(twavs)))
+    with_srmr, srmrs = getattr(opts, 'srmr', False), []
     beg_t = timeit.default_timer()
     for t_i, twav in enumerate(twavs, start=1):
         rate, wav = wavfile.read(twav)
@@ -98,13 +104,20 @@ def main(opts):
         g_wav, _g_c = segan.generate(pwav, device='cuda')
         out_path = os.path.join(opts.synthesis_path, os.path.basename(twav))
         g_wav, out_rate = np.asarray(g_wav, dtype=np.float32), int(16e3)
+        if with_srmr:
+            from segan_pytorch_amd import quality
+            srmrs.append(float(quality.srmr(torch.from_numpy(g_wav.reshape(-1)).cuda())[0]))
         if convert and keep_rate:
             g_wav = resample_wav(g_wav.reshape(-1), TARGET_RATE, rate, rs_zeros, rs_beta)[:n_in]
             out_rate = rate
         wavfile.write(out_path, out_rate, g_wav)
         end_t = timeit.default_timer()
         print('Cleaned {}/{}: {} in {} s'.format(t_i, len(twavs), twav, end_t - beg_t))
+        if with_srmr:
+            print('SRMR {}: {:.4f}'.format(out_path, srmrs[-1]))
         beg_t = timeit.default_timer()
+    if with_srmr:
+        print('mean SRMR: ', np.nanmean(srmrs) if srmrs else float('nan'))
 
 
 if __name__ == '__main__':

@@ -2,7 +2,8 @@
 the clean wavs of the same names, on the MI355X: the reference's eval_noisy_performance.py.
 
     python eval_noisy_performance.py --test_wavs DIR --clean_wavs DIR --logfile FILE [--stoi]
-                                     [--estoi] [--fwsegsnr] [--cd] [--sisdr] [--sdr] [--resample]
+                                     [--estoi] [--fwsegsnr] [--cd] [--sisdr] [--sdr] [--srmr]
+                                     [--resample]
 
 16 kHz wavs only (int16 files are scaled by 1/32768, float files used as they are), unless
 --resample converts files of other rates to 16 kHz on the GPU first (int16 files to int16, float
@@ -15,7 +16,9 @@ columns FWSEGSNR (quality.fwsegsnr, frequency-weighted segmental SNR in dB), CD
 (quality.cepstral_distance, LPC cepstrum distance) and SISDR (quality.si_sdr, scale-invariant SDR
 in dB) with their final mean lines; none of the three needs pesqmain.  --sdr adds, after them, the
 column SDR (quality.sdr, the BSS-eval signal-to-distortion ratio in dB with a 512-tap distortion
-filter) and its mean line."""
+filter) and its mean line.  --srmr adds, last, the column SRMR (quality.srmr, the
+speech-to-reverberation modulation energy ratio of the degraded file alone: it needs no clean
+signal) and its mean line."""
 import argparse
 import glob
 import os
@@ -56,7 +59,8 @@ def read_wav(path, opts=None):
 # the optional columns in their order: (column, flag, function of segan_pytorch_amd.quality)
 EXTRA = (('STOI', 'stoi', 'stoi'), ('ESTOI', 'estoi', 'estoi'),
          ('FWSEGSNR', 'fwsegsnr', 'fwsegsnr'), ('CD', 'cd', 'cepstral_distance'),
-         ('SISDR', 'sisdr', 'si_sdr'), ('SDR', 'sdr', 'sdr'))
+         ('SISDR', 'sisdr', 'si_sdr'), ('SDR', 'sdr', 'sdr'), ('SRMR', 'srmr', 'srmr'))
+BLIND = ('SRMR',)     # columns computed on the degraded file alone
 
 
 def header_line(opts):
@@ -73,7 +77,7 @@ def main(opts):
     extra = [(name, getattr(quality, fn)) for name, flag, fn in EXTRA if getattr(opts, flag)]
     noisy_wavs = sorted(glob.glob(os.path.join(opts.test_wavs, '*.wav')))
     metrics = {'csig': [], 'cbak': [], 'covl': [], 'STOI': [], 'ESTOI': [], 'FWSEGSNR': [],
-               'CD': [], 'SISDR': [], 'SDR': []}
+               'CD': [], 'SISDR': [], 'SDR': [], 'SRMR': []}
     timings = []
     with open(opts.logfile, 'w') as out_log:
         out_log.write(header_line(opts) + '\n')
@@ -90,7 +94,10 @@ def main(opts):
                 L = min(len(clean), len(noisy))
                 c, d = torch.from_numpy(clean[:L]).cuda(), torch.from_numpy(noisy[:L]).cuda()
                 for name, fn in extra:
-                    metrics[name].append(float(fn(c, d)[0]))
+                    if name in BLIND:
+                        metrics[name].append(float(fn(torch.from_numpy(noisy).cuda())[0]))
+                    else:
+                        metrics[name].append(float(fn(c, d)[0]))
             end_t = timeit.default_timer()
             timings.append(end_t - beg_t)
             metrics['csig'].append(csig)
@@ -130,6 +137,9 @@ def build_parser():
     parser.add_argument('--sdr', action='store_true', default=False,
                         help='also compute SDR (BSS-eval signal-to-distortion ratio with a '
                              '512-tap distortion filter, dB)')
+    parser.add_argument('--srmr', action='store_true', default=False,
+                        help='also compute SRMR (speech-to-reverberation modulation energy ratio '
+                             'of the degraded file alone)')
     parser.add_argument('--resample', action='store_true', default=False,
                         help='convert wavs that are not 16 kHz to 16 kHz on the GPU instead of '
                              'refusing them')

@@ -498,6 +498,43 @@ int segan_sdr(const float* ref, const float* deg, const int* lengths, int rows, 
               double* row_out, double* stages_out, double* ws, void* stream);
 int segan_toeplitz_solve(const double* r, const double* d, int rows, int n, double* c_out,
                          int* order_out, void* stream);
+/* SRMR, the speech-to-reverberation modulation energy ratio of Falk, Zheng and Chan (2010): the
+ * time-domain measure with 23 gammatone channels and 8 modulation bands, no energy normalisation;
+ * it needs no clean signal.  fp64 on fp32 rows x [rows][T] at `rate` (8000 or 16000), row r
+ * restricted to its first lengths[r] = N samples (device int[rows], clamped to 0 .. T; NULL: all
+ * T); DESIGN.md section 16, scripts/srmr_oracle.py.  Per row:
+ *   the gammatone channels (four cascaded biquads each, zero state, sequential in time); the
+ *   envelope |analytic(y)| on the row zero-padded to its own L, the smallest power of two >= N;
+ *   the eight Q = 2 modulation band-passes; E[i][k][f] = sum (w m)^2 over the full frames of
+ *   ceil(0.256 rate) samples every ceil(0.064 rate), w the periodic Hamming window; Ebar the mean
+ *   over the frames in ascending order; BW = ERB of the first channel, from the lowest centre
+ *   frequency upwards, at which the cumulated share of sum_k Ebar exceeds 90 %; K* = 5 .. 8 from
+ *   BW against the bands' left cutoffs (5 where BW lies at or below the fifth band's);
+ *   row_out[rows] = sum_i sum_{k<4} Ebar / sum_i sum_{4<=k<K*} Ebar; NaN for a row shorter than
+ *   one frame or without energy.
+ * No atomics, every sum and recurrence in an order fixed by the sample index: a row's bits depend
+ * neither on T, nor on the other rows, nor on the samples past its length, and a row times a
+ * power of two gives the same bits.
+ *   segan_srmr_dims (host only): out[4] = {L of T, the frames of T, the doubles of workspace per
+ *     row, the doubles of segan_srmr's workspace `ws` for `rows` rows}.
+ *   segan_srmr: ws 16-byte aligned; stages_out (may be NULL) [rows][SEGAN_SRMR_STAGE]: the centre
+ *     frequencies [23], sum e_i^2 over the N samples [23], Ebar [23][8], BW, K*, the cumulated
+ *     share that decided BW, the value.
+ *   segan_fft_z2z: the batched complex fp64 transform of n = 2^log2n points on its own, in / out
+ *     [rows][n] interleaved (re, im), 16-byte aligned; inverse != 0: the inverse with 1/n.
+ *     n <= 2^SEGAN_FFT_LDS_LOG2 runs in LDS and may be in place; larger n as two levels, in != out.
+ * rows in 1 .. 65535, T in 1 .. 2^SEGAN_FFT_MAX_LOG2, log2n in 1 .. SEGAN_FFT_MAX_LOG2, checked
+ * before any launch.  Added without a change of SEGAN_ABI_VERSION: the exports are purely
+ * additive. */
+#define SEGAN_SRMR_CHANNELS 23
+#define SEGAN_SRMR_BANDS 8
+#define SEGAN_SRMR_STAGE 234
+#define SEGAN_FFT_LDS_LOG2 12
+#define SEGAN_FFT_MAX_LOG2 20
+int segan_fft_z2z(const double* in, double* out, int rows, int log2n, int inverse, void* stream);
+int segan_srmr_dims(int rows, int T, int rate, long long* out);
+int segan_srmr(const float* x, const int* lengths, int rows, int T, int rate, double* row_out,
+               double* stages_out, double* ws, void* stream);
 
 /* ---- on-the-fly additive noise (the reference's Additive, utils.py:43-297)
  * fp64 arithmetic on fp32 rows x / clean [rows][T], row r restricted to its first lengths[r]

@@ -13,8 +13,13 @@ utterance like eval_noisy_performance.py, with a device synchronise; prints one 
         # SDR, 512 taps) over the same set, and the numpy oracle scripts/sdr_oracle.py on
         # --sdr-cpu of its utterances; the JSON line also goes to --sdr-out
         # (profiles/sdr_bench.json)
+    python scripts/bench_quality.py --srmr       # instead: ONE call of quality.srmr over the degraded
+        # signals of the same set (ops.srmr chunks it under its workspace cap), and the numpy /
+        # scipy oracle scripts/srmr_oracle.py on --srmr-cpu of its utterances; the JSON line also
+        # goes to --srmr-out (profiles/srmr_bench.json)
 """
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -50,8 +55,19 @@ def main():
                     help='time the batched BSS-eval SDR call and its numpy oracle instead')
     ap.add_argument('--sdr-cpu', type=int, default=3)
     ap.add_argument('--sdr-out', default=os.path.join(ROOT, 'profiles', 'sdr_bench.json'))
+    ap.add_argument('--srmr', action='store_true',
+                    help='time the batched SRMR call and its numpy / scipy oracle instead')
+    ap.add_argument('--srmr-cpu', type=int, default=3)
+    ap.add_argument('--srmr-out', default=os.path.join(ROOT, 'profiles', 'srmr_bench.json'))
     args = ap.parse_args()
     utts = utterances()
+    if args.srmr:
+        import torch
+        out = batched_srmr(torch, utts, args.batch_reps, args.srmr_cpu)
+        with open(args.srmr_out, 'w') as f:
+            f.write(json.dumps(out) + '\n')
+        print(json.dumps(out))
+        return
     if args.sdr:
         import torch
         out = batched_sdr(torch, utts, args.batch_reps, args.sdr_cpu)
@@ -162,6 +178,55 @@ def batched_sdr(torch, utts, reps, ncpu):
             'sdr_nonfinite_rows': int((~torch.isfinite(v)).sum()),
             'oracle_cpu_utts': ncpu, 'oracle_cpu_s_per_utt': cpu,
             'max_abs_diff_db_vs_oracle': max([abs(a - b) for a, b in zip(got, want)] or [0.0])}
+
+
+def batched_srmr(torch, utts, reps, ncpu):
+    """Seconds of one quality.srmr call over the degraded signals of the whole set (after one
+    warm-up call, mean of `reps`, up to a device synchronise; ops.srmr walks the rows in chunks
+    under its workspace cap), the oracle's seconds per utterance on the first `ncpu` utterances,
+    and the largest relative difference between the two on those."""
+    sys.path.insert(0, os.path.join(ROOT, 'scripts'))
+    import srmr_oracle
+    from segan_pytorch_amd import _lib, ops, quality
+    lengths = [len(d) for _, d in utts]
+    deg = torch.zeros(len(utts), max(lengths))
+    for i, (_, d) in enumerate(utts):
+        deg[i, :len(d)] = torch.from_numpy(d)
+    deg = deg.cuda()
+    v = quality.srmr(deg, lengths=lengths)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        v = quality.srmr(deg, lengths=lengths)
+    torch.cuda.synchronize()
+    dt = (time.perf_counter() - t0) / reps
+    dims = (ctypes.c_int64 * 4)()
+    _lib.load().segan_srmr_dims(len(utts), max(lengths), 16000, dims)
+    # the same with a cap that takes the whole set in one call of segan_srmr
+    whole = 8 * dims[3] + 64
+    one = ops.srmr(deg, lengths=lengths, ws_cap=whole)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        one = ops.srmr(deg, lengths=lengths, ws_cap=whole)
+    torch.cuda.synchronize()
+    dt_one = (time.perf_counter() - t0) / reps
+    same = bool(torch.equal(one.view(torch.int64), v.view(torch.int64)))
+    t0 = time.perf_counter()
+    want = [srmr_oracle.srmr(d) for _, d in utts[:ncpu]]
+    cpu = (time.perf_counter() - t0) / max(ncpu, 1)
+    got = v[:ncpu].cpu().tolist()
+    return {'leg': 'mi355x', 'measure': 'srmr', 'utts': len(utts),
+            'mean_audio_s': float(np.mean(lengths)) / 16000, 'batched_seconds': dt,
+            'batched_utts_per_s': len(utts) / dt, 'mean_srmr': float(v[torch.isfinite(v)].mean()),
+            'srmr_nonfinite_rows': int((~torch.isfinite(v)).sum()),
+            'ws_cap_bytes': ops.SRMR_WS_CAP, 'ws_bytes_per_row': 8 * dims[2],
+            'calls': -(-len(utts) // max(1, ops.SRMR_WS_CAP // (8 * dims[2]))),
+            'one_call_ws_bytes': whole, 'one_call_seconds': dt_one,
+            'one_call_utts_per_s': len(utts) / dt_one, 'one_call_same_bits': same,
+            'oracle_cpu_utts': ncpu, 'oracle_cpu_s_per_utt': cpu,
+            'max_rel_diff_vs_oracle': max([abs(a - b) / abs(b) for a, b in zip(got, want)]
+                                          or [0.0])}
 
 
 if __name__ == '__main__':

@@ -106,6 +106,9 @@ SIGNATURES = {
     'segan_sdr_dims': (c_int, [c_int, c_int, c_int, POINTER(c_int64)]),
     'segan_sdr': (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P]),
     'segan_toeplitz_solve': (c_int, [_P, _P, c_int, c_int, _P, _P, _P]),
+    'segan_fft_z2z': (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    'segan_srmr_dims': (c_int, [c_int, c_int, c_int, POINTER(c_int64)]),
+    'segan_srmr': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P]),
     'segan_asl_p56': (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     'segan_additive_mix': (c_int, [_P, _P, _P, c_int64, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P]),
     'segan_resample_plan': (c_int, [c_int, c_int, c_int, c_double, POINTER(c_int), POINTER(c_int), _P, c_int]),

@@ -425,7 +425,9 @@ class SEGAN(Model):
         with `opts.eval_estoi` (train.py --eval_estoi) a key 'estoi' (quality.estoi) likewise,
         and with `opts.eval_fwsegsnr` / `eval_cd` / `eval_sisdr` the keys 'fwsegsnr', 'cd',
         'sisdr' (quality.fwsegsnr, quality.cepstral_distance, quality.si_sdr), and with
-        `opts.eval_sdr` the key 'sdr' (quality.sdr, BSS-eval SDR with a 512-tap filter).
+        `opts.eval_sdr` the key 'sdr' (quality.sdr, BSS-eval SDR with a 512-tap filter).  With
+        `opts.eval_srmr` the key 'srmr' (quality.srmr) is the speech-to-reverberation modulation
+        energy ratio of the enhanced (noisy) signal alone: it uses no clean signal.
         De-emphasis runs along time (the reference applies it along axis 0 of the [B, T] batch,
         model.py:474-477)."""
         from .. import ops, quality
@@ -437,9 +439,10 @@ class SEGAN(Model):
                                       ('cd', quality.cepstral_distance),
                                       ('sisdr', quality.si_sdr), ('sdr', quality.sdr))
                 if bool(getattr(opts, 'eval_' + k, False))]
+        with_srmr = bool(getattr(opts, 'eval_srmr', False))
         keys = ('ssnr', 'snr', 'pesq', 'csig', 'cbak', 'covl', 'wss', 'llr') + (
             ('stoi',) if with_stoi else ()) + (('estoi',) if with_estoi else ()) + tuple(
-                k for k, _ in more)
+                k for k, _ in more) + (('srmr',) if with_srmr else ())
         evals = {k: [] for k in keys}
         noisy_evals = {k: [] for k in keys}
         workers = getattr(opts, 'eval_workers', 2)
@@ -466,6 +469,8 @@ class SEGAN(Model):
                         dst['estoi'] += quality.estoi(c, d).cpu().tolist()
                     for k, fn in more:
                         dst[k] += fn(c, d).cpu().tolist()
+                    if with_srmr:
+                        dst['srmr'] += quality.srmr(d).cpu().tolist()
                 if bidx >= max_samples:
                     break
         self.G.train()

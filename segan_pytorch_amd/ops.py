@@ -1326,6 +1326,99 @@ def toeplitz_solve(r, d):
     return c.reshape(r.shape), order
 
 
+FFT_MAX_LOG2 = 20        # SEGAN_FFT_MAX_LOG2 (include/segan_hip.h): the longest transform, 2^20
+FFT_LDS_LOG2 = 12        # SEGAN_FFT_LDS_LOG2: up to 2^12 points one workgroup transforms in LDS
+SRMR_CHANNELS = 23       # SEGAN_SRMR_CHANNELS: gammatone channels
+SRMR_BANDS = 8           # SEGAN_SRMR_BANDS: modulation bands
+SRMR_STAGE = 234         # SEGAN_SRMR_STAGE: doubles of one row's stage block
+SRMR_RATES = (8000, 16000)
+SRMR_WS_CAP = 1 << 30    # bytes of workspace one call of segan_srmr may take
+
+
+def fft_pow2(x, inverse=False):
+    """The discrete Fourier transform of each row of x ([rows, n] or [n] complex128 CUDA tensor,
+    n a power of two from 2 to 2^20) on the device, numpy.fft.fft's sign and scaling
+    (`inverse=True`: numpy.fft.ifft's, with 1/n).  Up to n = 4096 one workgroup transforms a row
+    in LDS; above that the transform runs as two levels.  Returns a new tensor like x."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError('x must be a tensor, got {}'.format(type(x)))
+    if not x.is_cuda:
+        raise RuntimeError('x is on {}: segan_pytorch_amd runs only on an MI355X (HIP) device; '
+                           'there is no CPU path'.format(x.device))
+    if x.dtype != torch.complex128:
+        raise TypeError('x must be complex128, got {}'.format(x.dtype))
+    if x.dim() not in (1, 2):
+        raise ValueError('fft_pow2: x must be [rows, n] or [n], got {}'.format(tuple(x.shape)))
+    x2 = x.reshape(-1, x.shape[-1]).contiguous()
+    rows, n = x2.shape
+    lg = n.bit_length() - 1
+    if not 1 <= rows <= 65535 or n < 2 or n != 1 << lg or lg > FFT_MAX_LOG2:
+        raise ValueError('fft_pow2: 1 .. 65535 rows of a power of two from 2 to 2^{} values, got '
+                         '{}'.format(FFT_MAX_LOG2, tuple(x.shape)))
+    out = torch.empty_like(x2)
+    check(_lib.load().segan_fft_z2z(_ptr(x2), _ptr(out), rows, lg, 1 if inverse else 0,
+                                    _stream()), 'fft_pow2')
+    return out.reshape(x.shape)
+
+
+def srmr_stages(x, lengths=None, rate=16000, ws_cap=SRMR_WS_CAP):
+    """Every stage of `srmr` of each row of x [rows, T] (fp32 CUDA tensor)
+    on the device, as a dict of fp64 tensors: 'cfs' [23] (the gammatone centre frequencies,
+    descending), 'envelope_energy' [rows, 23] (the sum of each channel's squared Hilbert envelope
+    over the row's samples), 'energy' [rows, 23, 8] (the modulation energies, means over the
+    frames), 'bw' [rows] (the ERB of the channel below which 90 % of the energy lies), 'kstar'
+    [rows] (int64: 5 .. 8, the modulation bands counted; 0 for a NaN row), 'share' [rows] (the
+    cumulated share in per cent that decided 'bw') and 'srmr' [rows].  Row r is x[r, :lengths[r]]
+    (host integers 0 .. T; all T without `lengths`).  The rows are processed in chunks whose
+    workspace stays under `ws_cap` bytes; the result is bit for bit the same for every chunking.
+    No device-to-host copy."""
+    _chk(x, 'x', 2)
+    rows, T = x.shape
+    if not 1 <= rows <= 65535 or not 1 <= T <= 1 << FFT_MAX_LOG2:
+        raise ValueError('srmr: 1 .. 65535 rows of 1 .. 2^{} samples, got {}'.format(
+            FFT_MAX_LOG2, tuple(x.shape)))
+    if isinstance(rate, bool) or rate not in SRMR_RATES:
+        raise ValueError('srmr: rate must be one of {}, got {!r}'.format(SRMR_RATES, rate))
+    lens = None if lengths is None else _row_lengths('srmr', lengths, rows, T, x.device)
+    lib = _lib.load()
+    dims = (ctypes.c_int64 * 4)()
+    check(lib.segan_srmr_dims(rows, T, rate, dims), 'srmr')
+    cap = _int_arg(ws_cap, 'srmr: ws_cap', 1, 1 << 62)
+    per = int(cap // (8 * dims[2]))
+    if per < 1:
+        raise ValueError('srmr: ws_cap of {} bytes is below the {} bytes one row of {} samples '
+                         'needs'.format(cap, 8 * dims[2], T))
+    per = min(per, rows)
+    ws = _stream_scratch(8 * dims[2] * per + 16, x.device)
+    ws = ws[(-ws.data_ptr()) % 16:]
+    out = torch.empty(rows, device=x.device, dtype=torch.float64)
+    stages = torch.empty((rows, SRMR_STAGE), device=x.device, dtype=torch.float64)
+    for r0 in range(0, rows, per):
+        n = min(per, rows - r0)
+        check(lib.segan_srmr(_ptr(x[r0:r0 + n]), _ptr(None if lens is None else lens[r0:r0 + n]),
+                             n, T, rate, _ptr(out[r0:r0 + n]), _ptr(stages[r0:r0 + n]), _ptr(ws),
+                             _stream()), 'srmr')
+    C, P = SRMR_CHANNELS, SRMR_CHANNELS * SRMR_BANDS
+    return {'cfs': stages[0, :C], 'envelope_energy': stages[:, C:2 * C],
+            'energy': stages[:, 2 * C:2 * C + P].reshape(rows, C, SRMR_BANDS),
+            'bw': stages[:, 2 * C + P], 'kstar': stages[:, 2 * C + P + 1].to(torch.int64),
+            'share': stages[:, 2 * C + P + 2], 'srmr': out}
+
+
+def srmr(x, lengths=None, rate=16000, ws_cap=SRMR_WS_CAP):
+    """SRMR, the speech-to-reverberation modulation energy ratio (Falk, Zheng and Chan 2010), of
+    each row of x [rows, T] at `rate` (16000 or 8000) on the device: the energy of the envelope
+    modulations below about 20 Hz, where speech lives, over that of the faster ones, which
+    reverberation and noise fill; higher is better, and no clean signal is needed.  23 gammatone
+    channels, 8 modulation bands, no energy normalisation; K*, the number of bands counted, is 5
+    where the 90 % bandwidth lies at or below the fifth band's left cutoff, which the authors'
+    toolbox leaves undefined.  fp64 [rows]; NaN for a row shorter than one frame of
+    ceil(0.256 rate) samples or without energy.  Fixed operation order: a batched row equals its
+    own call bit for bit, and a row times a power of two gives the same bits.  `lengths`,
+    `ws_cap` as in `srmr_stages`."""
+    return srmr_stages(x, lengths, rate, ws_cap)['srmr']
+
+
 ASL_THRESHOLDS = 15      # nbits - 1 thresholds 2^-15 .. 2^-1 (nbits = 16)
 ADDITIVE_CAP = 1         # status bits of asl_p56 / additive_mix (include/segan_hip.h)
 ADDITIVE_PN0 = 2

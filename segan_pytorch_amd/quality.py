@@ -246,3 +246,12 @@ def sdr(ref, deg, lengths=None, taps=ops.SDR_TAPS):
     samples, a clean signal without energy or a processed signal of zeros; +inf where the
     processed signal is the clean one times a power of two."""
     return ops.sdr(*_same_shape_rows('sdr', ref, deg), lengths, taps)
+
+
+def srmr(x, srate=16000, lengths=None):
+    """SRMR, the speech-to-reverberation modulation energy ratio (Falk, Zheng and Chan 2010;
+    DESIGN.md section 16) of each row of x ([T] or [rows, T], fp32 on the device) at `srate` (16000
+    or 8000; `lengths`: per-row sample counts 0 .. T): fp64 tensor [rows], higher is better.  The
+    one measure here that needs no clean signal.  NaN for a row shorter than 0.256 s or without
+    energy."""
+    return ops.srmr(_as_rows(x, 'x').float().contiguous(), lengths, srate)

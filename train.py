@@ -79,6 +79,9 @@ FLAGS = [
     ('--eval_sdr', dict(action='store_true', default=False,
                         help='the evaluation also reports SDR (BSS-eval signal-to-distortion '
                              'ratio with a 512-tap distortion filter)')),
+    ('--eval_srmr', dict(action='store_true', default=False,
+                         help='the evaluation also reports SRMR (speech-to-reverberation '
+                              'modulation energy ratio; needs no clean signal)')),
     ('--slice_workers', dict(type=int, default=1)),
     ('--num_workers', dict(type=int, default=1)),
     ('--no-cuda', dict(action='store_true', default=False)),
