@@ -673,6 +673,54 @@ int segan_reverb_rows(const float* x, const int* lengths, const float* prev, con
                       const float* fwd, const float* inv, int rows, int T, int max_delay, float* ws,
                       int64_t ws_floats, float* y, float* prev_out, int* status, void* stream);
 
+/* ---- on-the-fly clipping, chunk removal and band limiting --------------
+ * Three signal-level distortions of fp32 rows x [rows][T], row r restricted to its first
+ * lengths[r] samples (device int[rows], clamped to 0 .. T; NULL: all T); rows <= 65535.  One
+ * workgroup per row (per tile of SEGAN_FIR_TILE outputs for the FIR), no atomics, no scratch: a
+ * row's result is bitwise independent of the other rows and of its position.  No product is
+ * contracted with a sum.
+ *   segan_clip_rows: m[r] = max |x[r][:len]| (exact), thr[r] = (float)((double)factor[r] *
+ *     (double)m[r]) with factor double[rows] on the device, y = min(max(x, -thr), thr); samples
+ *     from len on are copied.  prev / prev_out (both or neither) float[rows]: the sample preceding
+ *     the row, clamped the same way; it takes no part in m.  nclipped int[rows] = samples of the
+ *     row that changed.  status int[rows]: SEGAN_CLIP_ST_SILENT = m == 0 or len == 0,
+ *     SEGAN_CLIP_ST_FACTOR = factor outside (0, 1] (thr = 0); a flagged row, and its prev, is
+ *     copied unchanged.
+ *   segan_chop_rows: sample t < len is active when q[r][t] >= c0[r] (q double[rows][T], c0
+ *     double[rows]: the envelope and the threshold exactly as segan_asl_p56 writes them; no
+ *     hangover); n = nactive[r] is their number.  Slot c < C <= SEGAN_CHOP_MAX with dur[r][c] > 0
+ *     (int[rows][C], samples; <= 0: unused) takes k = min((long)floor(u[r][c] * (double)n), n - 1)
+ *     (u double[rows][C] in [0, 1)) and starts[r][c] = the index of the k-th active sample from 0
+ *     (-1 for an unused slot); y = 0 on the union of [start_c, min(start_c + dur_c, len)), x
+ *     elsewhere; nzeroed[r] = the size of the union.  status: SEGAN_CHOP_ST_NOLEVEL = c0 is NaN or
+ *     n == 0: the row is copied and every start is -1.  Integers throughout.
+ *   segan_fir_rows: row r is filtered with filter ids[r] of bank double[nf][kmax + 1] (one-sided
+ *     taps h[0 .. K[f]] of a symmetric filter, zeros after them; K int[nf]; kmax <=
+ *     SEGAN_FIR_MAX_K): with xe[-1] = prev[r] (0 without prev), xe[t] = x[t] for 0 <= t < len, 0
+ *     elsewhere,  y[n] = h[0] xe[n] + sum_{k = 1 .. K} h[k] (xe[n-k] + xe[n+k]),  n = -1 .. len-1,
+ *     in fp64 with k ascending: the inner sum first, then the product, then the accumulation, each
+ *     rounded on its own.  y[-1] goes to prev_out[r]; y[n] = 0 from len on.  y / prev_out are of
+ *     y_dtype: SEGAN_DT_F64, or SEGAN_DT_F32 (rounded once from the fp64 sum).  status:
+ *     SEGAN_FIR_ST_ID = the id is outside the bank (or its K outside 0 .. kmax): y = x, prev_out =
+ *     prev.  A sample's sum does not depend on the tile it falls in.
+ * Added without a change of SEGAN_ABI_VERSION: the exports are purely additive. */
+#define SEGAN_CLIP_ST_SILENT 1
+#define SEGAN_CLIP_ST_FACTOR 2
+#define SEGAN_CHOP_MAX 8
+#define SEGAN_CHOP_ST_NOLEVEL 1
+#define SEGAN_FIR_TILE 1024
+#define SEGAN_FIR_MAX_K 2048
+#define SEGAN_FIR_ST_ID 1
+int segan_clip_rows(const float* x, const int* lengths, const float* prev, const double* factor,
+                    int rows, int T, float* y, float* prev_out, float* m, float* thr,
+                    int* nclipped, int* status, void* stream);
+int segan_chop_rows(const float* x, const int* lengths, const double* q, const double* c0,
+                    const double* u, const int* dur, int rows, int T, int C, float* y, int* starts,
+                    int* nactive, int* nzeroed, int* status, void* stream);
+int segan_fir_rows(const float* x, const int* lengths, const float* prev, const double* bank,
+                   const int* K, int nf, int kmax, const int* ids, int rows, int T, void* y,
+                   int y_dtype, void* prev_out, int* status, void* stream);
+
 /* ---- optimizers (model.py:219-228) ---------------------------------------------------- */
 /* torch.optim.RMSprop (no momentum, not centered): sq = alpha*sq + (1-alpha)*g*g;
  * p -= lr * g / (sqrt(sq) + eps), over a flat arena of n floats. */

@@ -128,6 +128,10 @@ SIGNATURES = {
                                     c_int, c_int, _P]),
     'segan_reverb_rows': (c_int, [_P, _P, _P, _P, c_int64, _P, _P, c_int, _P, _P, c_int, c_int, c_int,
                                   _P, c_int64, _P, _P, _P, _P]),
+    'segan_clip_rows': (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
+    'segan_chop_rows': (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
+    'segan_fir_rows': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, c_int, c_int, _P, c_int, _P, _P,
+                               _P]),
     'segan_rmsprop_step': (c_int, [_P, _P, _P, c_float, c_float, c_float, c_int64, _P]),
     'segan_adam_step': (c_int, [_P, _P, _P, _P, c_float, c_double, c_double, c_float, c_int, c_int64,
                                 _P]),

@@ -2,7 +2,9 @@
 `Additive` (segan/utils.py:43-297) with the level measurement (ITU-T P.56 method B) and the mix as
 HIP kernels (`ops.asl_p56`, `ops.additive_mix`), batched.  And on-the-fly reverberation (section
 14): `Reverb` convolves each row with a room impulse response of an `RIRBank`
-(`ops.reverb_rows`)."""
+(`ops.reverb_rows`).  And three signal-level distortions (section 17): `Clip` (amplitude clipping,
+`ops.clip_rows`), `Chop` (chunks of speech removed, `ops.chop_rows`), `BandLimit` (a zero-phase
+low-pass, `ops.fir_rows`), and `Distort`, which applies one of them per row."""
 import glob
 import os
 
@@ -349,6 +351,278 @@ class Reverb(object):
         x = torch.from_numpy(np.ascontiguousarray(np.asarray(wav, dtype=np.float32).reshape(1, -1)))
         wet, _ = self.apply(x.cuda())
         return wet[0].cpu().type(torch.FloatTensor)
+
+
+# ---------------------------------------------------------------------------------
+# clipping, chunk removal and band limiting.  Every default below is this
+# project's own choice, not taken from a paper.
+# ---------------------------------------------------------------------------------
+DISTORT_KINDS = ('clip', 'chop', 'bandlimit')
+
+
+def _no_cpu():
+    if not torch.cuda.is_available():
+        raise RuntimeError('segan_pytorch_amd runs only on an MI355X (HIP) device; there is no '
+                           'CPU path')
+
+
+def _one_wave(wav):
+    if isinstance(wav, torch.Tensor):
+        wav = wav.detach().cpu().numpy()
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(wav, dtype=np.float32).reshape(1, -1)))
+
+
+class _RowDistortion(object):
+    """What Clip, Chop and BandLimit share: draws from a numpy Generator owned by the object
+    (`seed`), and `__call__(wav)` on one waveform (numpy array or tensor, any shape: flattened),
+    which returns a CPU FloatTensor like `Reverb.__call__`."""
+
+    def __call__(self, wav):
+        _no_cpu()
+        out, _ = self.apply(_one_wave(wav).cuda())
+        return out[0].cpu().type(torch.FloatTensor)
+
+
+class Clip(_RowDistortion):
+    """Amplitude clipping at `factor` times the row's own peak, one factor per row drawn uniformly
+    from `factors` (each in (0, 1]; 1.0 changes nothing)."""
+    kind = 'clip'
+
+    def __init__(self, factors=(0.1, 0.2, 0.3, 0.4, 0.5), seed=None):
+        self.factors = np.asarray(list(factors), dtype=np.float64).reshape(-1)
+        if len(self.factors) == 0 or not ((self.factors > 0) & (self.factors <= 1)).all():
+            raise ValueError('Clip: factors must be non-empty and lie in (0, 1], got {}'.format(
+                list(factors)))
+        self.rng = np.random.default_rng(seed)
+
+    def draw(self, rng, rows, factors=None):
+        """One factor per row (one vectorised draw); `factors` given are kept and not drawn."""
+        if factors is None:
+            return self.factors[rng.integers(len(self.factors), size=rows)]
+        f = np.asarray(factors, dtype=np.float64).reshape(-1)
+        if len(f) != rows or not ((f > 0) & (f <= 1)).all():
+            raise ValueError('Clip: {} factors in (0, 1] expected, got {}'.format(rows, f.tolist()))
+        return f
+
+    def apply(self, wave, generator=None, factors=None, lengths=None, prev=None):
+        """wave [B, T] (fp32 CUDA) -> (clipped [B, T], info).  info: the dict of `ops.clip_rows`
+        (m, thr, nclipped, status, and prev — the clamped sample preceding each row — when `prev`
+        is given) plus factors (numpy, host)."""
+        ops._chk(wave, 'wave', 2)
+        f = self.draw(self.rng if generator is None else generator, wave.shape[0], factors)
+        out, info = ops.clip_rows(wave, f, lengths, prev)
+        info.update(factors=f)
+        return out, info
+
+
+class Chop(_RowDistortion):
+    """Chunks of speech removed (dropouts): per row 1 .. `max_chops` chunks, each `durs[0]` ..
+    `durs[1]` seconds long, start where the P.56 envelope of the row is above its activity
+    threshold (`ops.asl_p56_stages`: q >= c0), so that speech and not a pause is hit.  A row
+    without a P.56 level (silence, or a level below the margin) is left unchanged
+    (ops.CHOP_NOLEVEL)."""
+    kind = 'chop'
+
+    def __init__(self, max_chops=3, durs=(0.05, 0.3), srate=16000, seed=None):
+        self.max_chops = ops._int_arg(max_chops, 'Chop: max_chops', 1, ops.CHOP_MAX)
+        self.srate = ops._int_arg(srate, 'Chop: srate', 1, 768000)
+        lo, hi = (float(d) for d in durs)
+        if not (0.0 < lo <= hi) or hi * self.srate >= 2 ** 31 or np.rint(lo * self.srate) < 1:
+            raise ValueError('Chop: durs must be 0 < lo <= hi seconds and at least a sample, got '
+                             '{}'.format(list(durs)))
+        self.durs = (lo, hi)
+        self.rng = np.random.default_rng(seed)
+
+    def draw(self, rng, rows):
+        """(u float64 [rows, max_chops], dur int32 [rows, max_chops]) from three vectorised draws
+        in this order: the rows' chunk counts (uniform over 1 .. max_chops), max_chops durations per
+        row (uniform over `durs`, rounded to samples) and max_chops positions u per row (uniform
+        over [0, 1)).  The slots from a row's count on are unused (dur = 0): every row consumes
+        the same number of draws whatever its count."""
+        C = self.max_chops
+        count = rng.integers(1, C + 1, size=rows)
+        dur = np.rint(rng.uniform(self.durs[0], self.durs[1], size=(rows, C)) * self.srate)
+        u = rng.random((rows, C))
+        dur = np.where(np.arange(C)[None, :] < count[:, None], dur, 0).astype(np.int32)
+        return u, dur
+
+    def apply(self, wave, generator=None, u=None, dur=None, lengths=None, prev=None):
+        """wave [B, T] (fp32 CUDA) -> (chopped [B, T], info).  `u`, `dur` ([B, C], both or
+        neither) replace the draws.  info: the dict of `ops.chop_rows` (starts, nactive, nzeroed,
+        status) plus c0 (device), u, dur (numpy, host) and prev: the incoming `prev`, untouched
+        (when given)."""
+        ops._chk(wave, 'wave', 2)
+        if (u is None) != (dur is None):
+            raise ValueError('Chop: u and dur go together')
+        if u is None:
+            u, dur = self.draw(self.rng if generator is None else generator, wave.shape[0])
+        level = ops.asl_p56_stages(wave, self.srate, 16, lengths)
+        out, info = ops.chop_rows(wave, level['q'], level['c0'], u, dur, lengths)
+        info.update(c0=level['c0'], u=u, dur=dur)
+        if prev is not None:
+            info['prev'] = prev
+        return out, info
+
+
+def lowpass_bank(cutoffs, srate=16000, zeros=32, beta=8.6):
+    """(bank float64 [nf, Kmax + 1], K int32 [nf]): per cutoff fc (Hz) the one-sided taps of a
+    zero-phase Kaiser-windowed sinc low-pass, built on the host in float64: K = ceil(zeros srate /
+    (2 fc)), h[k] = sinc(2 fc k / srate) w(k) with w the Kaiser window of half-length K and
+    parameter beta, scaled so that h[0] + 2 sum_{k>=1} h[k] = 1 (unit gain at DC; -6 dB at fc).
+    Rows are zero after their own K.  K > ops.FIR_MAX_K (a cutoff too low for `zeros`) raises
+    ValueError.  Restated by scripts/distort_oracle.py:lowpass: keep the two alike."""
+    fcs = np.asarray(list(cutoffs), dtype=np.float64).reshape(-1)
+    if len(fcs) == 0 or not ((fcs > 0) & (fcs < srate / 2.0)).all():
+        raise ValueError('lowpass_bank: cutoffs must be non-empty and lie in (0, {}) Hz, got '
+                         '{}'.format(srate / 2.0, fcs.tolist()))
+    if not (zeros >= 1 and 0.0 <= beta <= ops.RESAMPLE_BETA_MAX):
+        raise ValueError('lowpass_bank: zeros >= 1 and beta in 0 .. {} expected, got {}, {}'.format(
+            ops.RESAMPLE_BETA_MAX, zeros, beta))
+    Ks = [int(np.ceil(zeros * srate / (2.0 * fc))) for fc in fcs]
+    if max(Ks) > ops.FIR_MAX_K:
+        raise ValueError('lowpass_bank: cutoff {} Hz needs K = {} > {} taps a side'.format(
+            fcs[int(np.argmax(Ks))], max(Ks), ops.FIR_MAX_K))
+    bank = np.zeros((len(fcs), max(Ks) + 1), dtype=np.float64)
+    for f, (fc, K) in enumerate(zip(fcs, Ks)):
+        k = np.arange(K + 1, dtype=np.float64)
+        w = np.i0(beta * np.sqrt(np.maximum(0.0, 1.0 - (k / K) ** 2))) / np.i0(beta)
+        h = np.sinc(2.0 * fc * k / srate) * w
+        bank[f, :K + 1] = h / (h[0] + 2.0 * h[1:].sum())
+    return bank, np.asarray(Ks, dtype=np.int32)
+
+
+class BandLimit(_RowDistortion):
+    """Bandwidth reduction: each row is low-pass filtered at a cutoff drawn uniformly from
+    `cutoffs` (Hz) with a zero-phase FIR of `lowpass_bank`; the sample rate stays what it is."""
+    kind = 'bandlimit'
+
+    def __init__(self, cutoffs=(1000, 2000, 4000), srate=16000, zeros=32, beta=8.6, seed=None):
+        self.cutoffs = np.asarray(list(cutoffs), dtype=np.float64).reshape(-1)
+        self.bank, self.K = lowpass_bank(self.cutoffs, srate, zeros, beta)
+        self.srate = srate
+        self.rng = np.random.default_rng(seed)
+        self._dev = {}
+
+    def data(self, device):
+        """(bank, K) on `device` (a HIP device; uploaded once per device)."""
+        device = torch.device(device)
+        if device.type != 'cuda':
+            raise RuntimeError('BandLimit: segan_pytorch_amd runs only on an MI355X (HIP) device; '
+                               'there is no CPU path')
+        if device.index is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        if device not in self._dev:
+            with torch.cuda.device(device):
+                pair = (torch.from_numpy(self.bank).to(device), torch.from_numpy(self.K).to(device))
+                torch.cuda.current_stream(device).synchronize()      # other streams use it next
+            self._dev[device] = pair
+        return self._dev[device]
+
+    def draw(self, rng, rows, ids=None):
+        if ids is None:
+            return rng.integers(len(self.cutoffs), size=rows).astype(np.int64)
+        ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+        if len(ids) != rows or (ids < 0).any() or (ids >= len(self.cutoffs)).any():
+            raise ValueError('BandLimit: {} filter ids in 0 .. {} expected, got {}'.format(
+                rows, len(self.cutoffs) - 1, ids.tolist()))
+        return ids
+
+    def apply(self, wave, generator=None, ids=None, lengths=None, prev=None, out_dtype=None):
+        """wave [B, T] (fp32 CUDA) -> (filtered [B, T], info).  `ids` (per row) replaces the draw.
+        info: the dict of `ops.fir_rows` (prev = the filtered sample preceding each row, status)
+        plus ids, cutoffs (numpy, host)."""
+        ops._chk(wave, 'wave', 2)
+        ids = self.draw(self.rng if generator is None else generator, wave.shape[0], ids)
+        bank, K = self.data(wave.device)
+        out, info = ops.fir_rows(wave, bank, K, ids, lengths, prev, out_dtype)
+        info.update(ids=ids, cutoffs=self.cutoffs[ids])
+        return out, info
+
+
+class Distort(object):
+    """One of several distortions per row.  `kinds`: a list of `Clip` / `Chop` / `BandLimit`
+    objects, or a dict {'clip': ..., 'chop': ..., 'bandlimit': ...}; at most one of each.  `apply`
+    draws, from ONE generator and in this fixed order:
+      1. the kind of every row, uniform among the enabled kinds (one vectorised draw; the enabled
+         kinds are numbered in the order clip, chop, bandlimit);
+      2. clip's draws for its rows, in ascending row order (`Clip.draw`);
+      3. chop's draws for its rows likewise (`Chop.draw`);
+      4. bandlimit's draws for its rows likewise (`BandLimit.draw`).
+    Each op then runs on its own rows and the results are scattered back.  The generators of the
+    member objects are not used."""
+
+    def __init__(self, kinds, seed=None):
+        items = list(kinds.items()) if isinstance(kinds, dict) else [
+            (getattr(k, 'kind', None), k) for k in kinds]
+        self.ops = {}
+        for name, obj in items:
+            if name not in DISTORT_KINDS or not callable(getattr(obj, 'apply', None)):
+                raise ValueError('Distort: kinds must be Clip / Chop / BandLimit objects (names '
+                                 '{}), got {!r}'.format(list(DISTORT_KINDS), name))
+            if name in self.ops:
+                raise ValueError('Distort: {} is given twice'.format(name))
+            self.ops[name] = obj
+        if not self.ops:
+            raise ValueError('Distort: no kind enabled')
+        self.enabled = [k for k in DISTORT_KINDS if k in self.ops]
+        self.rng = np.random.default_rng(seed)
+
+    def draw_kinds(self, rng, rows):
+        return rng.integers(len(self.enabled), size=rows)
+
+    @staticmethod
+    def _index(a, device):
+        # pinned staging, asynchronous copy (see ops.additive_mix)
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).pin_memory().to(
+            device, non_blocking=True)
+
+    def apply(self, wave, generator=None, prev=None, lengths=None):
+        """wave [B, T] (fp32 CUDA) -> (out [B, T], info).  prev (optional fp32 CUDA [B]): the
+        sample preceding each row (zeros without it); lengths: host integers.  info: kinds (numpy
+        array of the rows' kind names, host), prev (device [B]: what a pre-emphasis that follows
+        needs — clamped by clip, untouched by chop, filtered by bandlimit), status (device int32
+        [B]: the row's own op's status) and, under each kind's name that got rows, that op's info
+        with `index` (numpy: its rows)."""
+        ops._chk(wave, 'wave', 2)
+        rows = wave.shape[0]
+        rng = self.rng if generator is None else generator
+        lens = None if lengths is None else np.asarray(torch.as_tensor(lengths).cpu(),
+                                                       dtype=np.int64).reshape(-1)
+        if lens is not None and len(lens) != rows:
+            raise ValueError('Distort: lengths must hold {} integers'.format(rows))
+        if prev is None:
+            prev = torch.zeros(rows, device=wave.device, dtype=torch.float32)
+        code = self.draw_kinds(rng, rows)
+        info = dict(kinds=np.asarray(self.enabled, dtype=object)[code])
+        out = prev_out = status = None
+        for c, name in enumerate(self.enabled):
+            idx = np.nonzero(code == c)[0]
+            if len(idx) == 0:
+                continue
+            sub_len = None if lens is None else lens[idx]
+            if len(idx) == rows:      # one kind for the whole batch: nothing to gather or scatter
+                out, sub = self.ops[name].apply(wave, generator=rng, prev=prev, lengths=sub_len)
+                prev_out, status = sub['prev'], sub['status']
+            else:
+                if out is None:
+                    out, prev_out = torch.empty_like(wave), torch.empty_like(prev)
+                    status = torch.empty(rows, device=wave.device, dtype=torch.int32)
+                idx_d = self._index(idx, wave.device)
+                y, sub = self.ops[name].apply(wave.index_select(0, idx_d), generator=rng,
+                                              prev=prev.index_select(0, idx_d), lengths=sub_len)
+                out.index_copy_(0, idx_d, y)
+                prev_out.index_copy_(0, idx_d, sub['prev'])
+                status.index_copy_(0, idx_d, sub['status'])
+            sub['index'] = idx
+            info[name] = sub
+        info.update(prev=prev_out, status=status)
+        return out, info
+
+    def __call__(self, wav):
+        """Distort one waveform (numpy array or tensor, any shape: flattened)."""
+        _no_cpu()
+        out, _ = self.apply(_one_wave(wav).cuda())
+        return out[0].cpu().type(torch.FloatTensor)
 
 
 class ComposeAdditive(object):

@@ -291,7 +291,8 @@ class PCMShardLoader(object):
     def __init__(self, shard, batch_size, preemph, device, sampler=None, drop_last=False,
                  num_workers=2, additive=None, additive_prob=1.0, additive_seed=None,
                  record_additive=False, reverb=None, reverb_prob=1.0, reverb_seed=None,
-                 record_reverb=False):
+                 record_reverb=False, distort=None, distort_prob=1.0, distort_seed=None,
+                 record_distort=False):
         from torch.utils.data import RandomSampler
         if additive is not None and not 0.0 <= float(additive_prob) <= 1.0:
             raise ValueError('additive_prob must lie in 0 .. 1, got {}'.format(additive_prob))
@@ -303,6 +304,11 @@ class PCMShardLoader(object):
         self.reverb, self.reverb_prob = reverb, float(reverb_prob)
         self.reverb_rng = np.random.default_rng(reverb_seed)      # its own stream of draws
         self.reverb_records = [] if record_reverb else None
+        if distort is not None and not 0.0 <= float(distort_prob) <= 1.0:
+            raise ValueError('distort_prob must lie in 0 .. 1, got {}'.format(distort_prob))
+        self.distort, self.distort_prob = distort, float(distort_prob)
+        self.distort_rng = np.random.default_rng(distort_seed)     # a third stream of draws
+        self.distort_records = [] if record_distort else None
         self.shard = shard
         self.sampler = sampler if sampler is not None else RandomSampler(shard)
         self.preemph = float(preemph)
@@ -333,6 +339,8 @@ class PCMShardLoader(object):
         wet = None
         if self.reverb is not None:
             names, wet = self._reverberate(names, pcm_d, first_d, noisy)
+        if self.distort is not None:
+            names, wet = self._distort(names, pcm_d, first_d, noisy, wet)
         if self.additive is not None:
             names = self._add_noise(names, pcm_d, first_d, noisy, wet)
         return [names, clean, noisy, idx]
@@ -374,6 +382,63 @@ class PCMShardLoader(object):
         return ([n + '_reverb' if i in chosen else n for i, n in enumerate(names)],
                 (sel, wet, info['prev']))
 
+    def _replace_rows(self, sel, wave, prev, done):
+        """wave [n, T] / prev [n] of the items `sel`, with the rows of items that an earlier stage
+        has already replaced (`done` = (items, waves, prevs), or None) copied over them."""
+        if done is None:
+            return
+        dsel, dwave, dprev = done
+        both, ia, ir = np.intersect1d(sel, dsel, assume_unique=True, return_indices=True)
+        if len(both):
+            ix = self._index_to_device(np.stack([ia, ir]))
+            wave.index_copy_(0, ix[0], dwave.index_select(0, ix[1]))
+            prev.index_copy_(0, ix[0], dprev.index_select(0, ix[1]))
+
+    def _distort(self, names, pcm_d, first_d, noisy, done):
+        """On-the-fly clipping, chunk removal or band limiting (augment.Distort, DESIGN.md section
+        17), after the reverberation and before any noise is mixed: each item is selected with
+        probability `distort_prob` from the loader's own distort generator, a third stream (the
+        reverb and additive selections and draws are the same with and without it).  A selected
+        item's wave is its reverberant wave if `_reverberate` selected it, else the fp32 min-max-
+        normalised clean slice; the sample preceding the slice is carried the same way (zero where
+        the slice starts its wav, the reverberant one after reverb).  The noisy row becomes the
+        pre-emphasised distorted wave — or, where the item is also selected for `additive`,
+        `_add_noise` mixes noise into the distorted wave first.  '_clip', '_chop' or '_bandlimit'
+        is appended to the name; `clean` is untouched.  `done`: the rows replaced so far (what
+        `_reverberate` returned); returns (names, done with this stage's rows merged in)."""
+        from . import ops
+        B, T = noisy.shape
+        sel = np.nonzero(self.distort_rng.random(B) < self.distort_prob)[0]
+        if len(sel) == 0:
+            if self.distort_records is not None:
+                self.distort_records.append(None)
+            return names, done
+        wave, prev = ops.pcm16_wave(pcm_d, sel)
+        sel_d = self._index_to_device(sel)
+        prev = prev.masked_fill(first_d.index_select(0, sel_d) != 0, 0.0)   # nothing precedes a wav
+        self._replace_rows(sel, wave, prev, done)
+        out, info = self.distort.apply(wave, generator=self.distort_rng, prev=prev)
+        ops.preemph_rows(out, info['prev'], first_d, noisy, self.preemph, sel)
+        if self.distort_records is not None:
+            info.update(index=sel, wave=wave, wave_prev=prev, out=out)
+            self.distort_records.append(info)
+        kind = dict(zip(sel.tolist(), info['kinds']))
+        names = [n + '_' + kind[i] if i in kind else n for i, n in enumerate(names)]
+        if done is not None:
+            # the earlier stage's rows that this one did not touch stay what they are
+            dsel, dwave, dprev = done
+            keep = np.nonzero(~np.isin(dsel, sel))[0]
+            if len(keep):
+                keep_d = self._index_to_device(keep)
+                items = np.concatenate((sel, dsel[keep]))
+                order = np.argsort(items, kind='stable')
+                order_d = self._index_to_device(order)
+                out = torch.cat((out, dwave.index_select(0, keep_d))).index_select(0, order_d)
+                oprev = torch.cat((info['prev'], dprev.index_select(0, keep_d))).index_select(
+                    0, order_d)
+                return names, (items[order], out, oprev)
+        return names, (sel, out, info['prev'])
+
     def _add_noise(self, names, pcm_d, first_d, noisy, wet=None):
         """On-the-fly additive noise (augment.Additive): each item is
         selected with probability `additive_prob`; a selected item's noisy row becomes clean +
@@ -386,8 +451,8 @@ class PCMShardLoader(object):
         rounded to fp32; when it does, y[0] = x[0].  The pre-emphasis is computed in double and
         rounded once, like the unaugmented rows.  Runs on the stream `_prep` runs on (the
         loader's side stream), between the H2D copy and the consumer; `clean` is untouched.
-        `wet`: what `_reverberate` returned; the wave of an item it selected is its reverberant
-        wave."""
+        `wet`: the rows that `_reverberate` / `_distort` have already replaced, with their prev:
+        the wave of such an item is its reverberant / distorted wave."""
         from . import ops
         B, T = noisy.shape
         sel = np.nonzero(self.additive_rng.random(B) < self.additive_prob)[0]
@@ -396,15 +461,9 @@ class PCMShardLoader(object):
                 self.additive_records.append(None)
             return names
         wave, prev = ops.pcm16_wave(pcm_d, sel)
-        if wet is not None:
-            # items that were reverberated: the level, sf and the divisions are taken on the
-            # reverberant wave, and the sample before the slice is the reverberant one
-            rsel, rwave, rprev = wet
-            both, ia, ir = np.intersect1d(sel, rsel, assume_unique=True, return_indices=True)
-            if len(both):
-                ix = self._index_to_device(np.stack([ia, ir]))
-                wave.index_copy_(0, ix[0], rwave.index_select(0, ix[1]))
-                prev.index_copy_(0, ix[0], rprev.index_select(0, ix[1]))
+        # items that were reverberated or distorted: the level, sf and the divisions are taken on
+        # that wave, and the sample before the slice is that wave's
+        self._replace_rows(sel, wave, prev, wet)
         mixed, info = self.additive.mix(wave, generator=self.additive_rng, prev=prev)
         ops.preemph_rows(mixed, info['prev'], first_d, noisy, self.preemph, sel)
         if self.additive_records is not None:

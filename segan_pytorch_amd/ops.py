@@ -8,6 +8,7 @@ tensor raises.
 import ctypes
 import operator
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1851,6 +1852,191 @@ def reverb_stages(x, bank, rir_ids, lengths=None, prev=None, X=None, yt=None):
                                   _ptr(prev_out), _ptr(status), rows, T, NB, M, _stream()),
           'reverb_finish')
     return dict(xs=xs, X=X, Y=Y, yt=yt, y=y, prev=prev_out, status=status, dims=dims)
+
+
+# ---------------------------------------------------------------------------------
+# clipping, chunk removal and band limiting
+# ---------------------------------------------------------------------------------
+DISTORT_MAX_ROWS = 65535
+CLIP_SILENT = 1          # status bits of clip_rows (SEGAN_CLIP_ST_*)
+CLIP_FACTOR = 2
+CHOP_MAX = 8             # SEGAN_CHOP_MAX: chunks per row
+CHOP_NOLEVEL = 1         # status bit of chop_rows
+FIR_MAX_K = 2048         # SEGAN_FIR_MAX_K: the longest one-sided filter
+FIR_TILE = 1024          # SEGAN_FIR_TILE: outputs per workgroup
+FIR_ID = 1               # status bit of fir_rows
+
+
+def _distort_rows(what, x, lengths, prev):
+    """The checks the three ops share; (rows, T, lens)."""
+    _chk(x, 'x', 2)
+    rows, T = x.shape
+    if rows == 0 or T == 0:
+        raise ValueError('{}: empty input {}'.format(what, tuple(x.shape)))
+    if rows > DISTORT_MAX_ROWS:
+        raise ValueError('{}: 1 .. {} rows, got {}'.format(what, DISTORT_MAX_ROWS, rows))
+    if lengths is None:
+        lens = None
+    elif isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+        if lengths.dtype != torch.int32 or lengths.shape != (rows,) or lengths.device != x.device:
+            raise ValueError('{}: device lengths must be int32 [{}] on {}'.format(what, rows,
+                                                                                  x.device))
+        lens = lengths.contiguous()
+    else:
+        lens = _row_lengths(what, lengths, rows, T, x.device)
+    if prev is not None:
+        _chk(prev, 'prev', 1)
+        if prev.numel() != rows or prev.device != x.device:
+            raise ValueError('{}: prev must hold {} values on {}'.format(what, rows, x.device))
+    return rows, T, lens
+
+
+def _distort_arg(what, name, v, shape, dtype, device, check_host=None):
+    """A per-row argument: a CUDA tensor of `dtype` and `shape` is used as it is (its values are
+    the caller's business: the kernels flag what they cannot use); host values are checked by
+    `check_host` and travel through pinned memory in an asynchronous copy (see additive_mix)."""
+    if isinstance(v, torch.Tensor) and v.is_cuda:
+        if v.dtype != dtype or tuple(v.shape) != tuple(shape) or v.device != device:
+            raise ValueError('{}: device {} must be {} {} on {}, got {} {}'.format(
+                what, name, dtype, list(shape), device, v.dtype, list(v.shape)))
+        return v.contiguous()
+    # through numpy: python floats stay float64 (torch.as_tensor would make them float32)
+    t = v.detach().cpu() if isinstance(v, torch.Tensor) else torch.from_numpy(np.asarray(v))
+    n = 1
+    for s in shape:
+        n *= s
+    if t.numel() != n or t.dtype in (torch.bool, torch.complex64, torch.complex128):
+        raise ValueError('{}: {} must hold {} values, got {}'.format(what, name, list(shape),
+                                                                     list(t.shape)))
+    if not dtype.is_floating_point and t.dtype.is_floating_point:
+        raise ValueError('{}: {} must be integers'.format(what, name))
+    t = t.reshape(shape)
+    if check_host is not None:
+        check_host(t)
+    return t.to(dtype).contiguous().pin_memory().to(device, non_blocking=True)
+
+
+def clip_rows(x, factors, lengths=None, prev=None):
+    """Amplitude clipping of each row of x [rows, T] (fp32 CUDA) at a fraction of its own peak
+    (DESIGN.md section 17): m = max |x[r, :len]|, thr = float32(float64(factor) * m), y = min(max(
+    x, -thr), thr).  factors [rows]: host numbers in (0, 1] (anything else is refused here), or a
+    CUDA float64 tensor (a value outside (0, 1] then gives status CLIP_FACTOR and the row
+    unchanged).  lengths: host integers or a CUDA int32 tensor; samples past a row's length are
+    copied.  prev (optional fp32 CUDA [rows]): the sample preceding each row, clamped like the row
+    (it takes no part in m) and returned as info['prev'].  Returns (y, info) with info = dict(m,
+    thr fp32 [rows], nclipped int32 [rows] (samples changed), status int32 [rows]: CLIP_SILENT (m
+    == 0 or an empty row: unchanged) | CLIP_FACTOR).  No device-to-host copy."""
+    rows, T, lens = _distort_rows('clip_rows', x, lengths, prev)
+
+    def ok(t):
+        f = t.to(torch.float64)
+        if not bool(((f > 0) & (f <= 1)).all()):
+            raise ValueError('clip_rows: factors must lie in (0, 1], got {}'.format(f.tolist()))
+
+    f_d = _distort_arg('clip_rows', 'factors', factors, (rows,), torch.float64, x.device, ok)
+    y = torch.empty_like(x)
+    prev_out = torch.empty_like(prev) if prev is not None else None
+    m = torch.empty(rows, device=x.device, dtype=torch.float32)
+    thr = torch.empty(rows, device=x.device, dtype=torch.float32)
+    ncl = torch.empty(rows, device=x.device, dtype=torch.int32)
+    status = torch.empty(rows, device=x.device, dtype=torch.int32)
+    check(_lib.load().segan_clip_rows(_ptr(x), _ptr(lens), _ptr(prev), _ptr(f_d), rows, T, _ptr(y),
+                                      _ptr(prev_out), _ptr(m), _ptr(thr), _ptr(ncl), _ptr(status),
+                                      _stream()), 'clip_rows')
+    info = dict(m=m, thr=thr, nclipped=ncl, status=status)
+    if prev is not None:
+        info['prev'] = prev_out
+    return y, info
+
+
+def chop_rows(x, q, c0, u, dur, lengths=None):
+    """Up to CHOP_MAX chunks of each row of x [rows, T] (fp32 CUDA) zeroed where there is speech
+    (DESIGN.md section 17).  q (fp64 CUDA [rows, T]) and c0 (fp64 CUDA [rows]) are the envelope and
+    the threshold of `asl_p56_stages`: sample t < len is active when q[t] >= c0 (no hangover), n of
+    them per row.  u [rows, C] in [0, 1) and dur [rows, C] >= 0 (samples; 0: an unused slot), host
+    values or CUDA float64 / int32 tensors: slot c starts at the k-th active sample, k =
+    min(floor(u n), n - 1), and zeroes [start, min(start + dur, len)).  Returns (y, info) with info
+    = dict(starts int32 [rows, C] (-1: unused), nactive, nzeroed (size of the union), status int32
+    [rows]: CHOP_NOLEVEL (c0 is NaN or nothing is active: the row unchanged, every start -1)).
+    Integer arithmetic throughout; no device-to-host copy."""
+    rows, T, lens = _distort_rows('chop_rows', x, lengths, None)
+    if not (isinstance(q, torch.Tensor) and q.is_cuda and q.dtype == torch.float64 and
+            tuple(q.shape) == (rows, T) and q.is_contiguous()):
+        raise TypeError('chop_rows: q must be a contiguous CUDA float64 tensor [{}, {}]'.format(
+            rows, T))
+    if not (isinstance(c0, torch.Tensor) and c0.is_cuda and c0.dtype == torch.float64 and
+            c0.numel() == rows):
+        raise TypeError('chop_rows: c0 must be a CUDA float64 tensor of {} values'.format(rows))
+    if q.device != x.device or c0.device != x.device:
+        raise ValueError('chop_rows: tensors on different devices')
+    ushape = tuple(u.shape) if hasattr(u, 'shape') else tuple(torch.as_tensor(u).shape)
+    if len(ushape) != 2 or ushape[0] != rows or not 1 <= ushape[1] <= CHOP_MAX:
+        raise ValueError('chop_rows: u must be [{}, C] with C from 1 to {}, got {}'.format(
+            rows, CHOP_MAX, list(ushape)))
+    C = ushape[1]
+
+    def u_ok(t):
+        f = t.to(torch.float64)
+        if not bool(((f >= 0) & (f < 1)).all()):
+            raise ValueError('chop_rows: u must lie in [0, 1), got {}'.format(f.tolist()))
+
+    def dur_ok(t):
+        if int(t.min()) < 0 or int(t.max()) >= 1 << 31:
+            raise ValueError('chop_rows: dur must lie in 0 .. 2^31 - 1, got {}'.format(t.tolist()))
+
+    u_d = _distort_arg('chop_rows', 'u', u, (rows, C), torch.float64, x.device, u_ok)
+    d_d = _distort_arg('chop_rows', 'dur', dur, (rows, C), torch.int32, x.device, dur_ok)
+    y = torch.empty_like(x)
+    starts = torch.empty((rows, C), device=x.device, dtype=torch.int32)
+    nact = torch.empty(rows, device=x.device, dtype=torch.int32)
+    nzero = torch.empty(rows, device=x.device, dtype=torch.int32)
+    status = torch.empty(rows, device=x.device, dtype=torch.int32)
+    check(_lib.load().segan_chop_rows(_ptr(x), _ptr(lens), _ptr(q), _ptr(c0.contiguous()),
+                                      _ptr(u_d), _ptr(d_d), rows, T, C, _ptr(y), _ptr(starts),
+                                      _ptr(nact), _ptr(nzero), _ptr(status), _stream()),
+          'chop_rows')
+    return y, dict(starts=starts, nactive=nact, nzeroed=nzero, status=status)
+
+
+def fir_rows(x, bank, K, ids, lengths=None, prev=None, out_dtype=None):
+    """Zero-phase FIR filtering of each row of x [rows, T] (fp32 CUDA) with filter ids[r] of a bank
+    of symmetric filters.  bank: fp64 CUDA [nf, Kmax + 1], the one-sided
+    taps h[0 .. K[f]] with zeros after them, Kmax <= FIR_MAX_K; K: int32 CUDA [nf]; ids [rows]:
+    host integers or a CUDA int32 tensor.  With xe[-1] = prev (0 without prev), xe = x on 0 ..
+    len-1 and zero elsewhere: y[n] = h[0] xe[n] + sum_k h[k] (xe[n-k] + xe[n+k]), k ascending, in
+    fp64 with every operation rounded on its own; y is zero from len on.  out_dtype: torch.float32
+    (default; rounded once from the fp64 sum) or torch.float64.  Returns (y, info): info['prev'] =
+    y[-1] ([rows], of out_dtype: what a pre-emphasis that follows needs), info['status'] int32
+    [rows]: FIR_ID (the id is not in the bank: the row unchanged).  No device-to-host copy."""
+    rows, T, lens = _distort_rows('fir_rows', x, lengths, prev)
+    out_dtype = torch.float32 if out_dtype is None else out_dtype
+    if out_dtype not in (torch.float32, torch.float64):
+        raise TypeError('fir_rows: out_dtype must be torch.float32 or torch.float64, got {}'.format(
+            out_dtype))
+    if not (isinstance(bank, torch.Tensor) and bank.is_cuda and bank.dtype == torch.float64 and
+            bank.dim() == 2 and bank.is_contiguous() and bank.shape[0] > 0 and bank.shape[1] > 0):
+        raise TypeError('fir_rows: bank must be a contiguous CUDA float64 tensor [nf, Kmax + 1]')
+    nf, kmax = bank.shape[0], bank.shape[1] - 1
+    if kmax > FIR_MAX_K:
+        raise ValueError('fir_rows: Kmax = {} exceeds {}'.format(kmax, FIR_MAX_K))
+    if not (isinstance(K, torch.Tensor) and K.is_cuda and K.dtype == torch.int32 and
+            tuple(K.shape) == (nf,) and K.is_contiguous()):
+        raise TypeError('fir_rows: K must be a contiguous CUDA int32 tensor [{}]'.format(nf))
+    if bank.device != x.device or K.device != x.device:
+        raise ValueError('fir_rows: tensors on different devices')
+
+    def ids_ok(t):
+        if int(t.min()) < -(1 << 31) or int(t.max()) >= 1 << 31:
+            raise ValueError('fir_rows: ids do not fit 32 bits')
+
+    ids_d = _distort_arg('fir_rows', 'ids', ids, (rows,), torch.int32, x.device, ids_ok)
+    y = torch.empty((rows, T), device=x.device, dtype=out_dtype)
+    prev_out = torch.empty(rows, device=x.device, dtype=out_dtype)
+    status = torch.empty(rows, device=x.device, dtype=torch.int32)
+    check(_lib.load().segan_fir_rows(_ptr(x), _ptr(lens), _ptr(prev), _ptr(bank), _ptr(K), nf, kmax,
+                                     _ptr(ids_d), rows, T, _ptr(y), _RESAMPLE_DT[out_dtype],
+                                     _ptr(prev_out), _ptr(status), _stream()), 'fir_rows')
+    return y, dict(prev=prev_out, status=status)
 
 
 def rmsprop_step(p, g, sq, lr, alpha, eps):

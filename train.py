@@ -12,7 +12,11 @@ batches are normalised / pre-emphasised on the GPU (with `--additive_noises DIR`
 into them on the fly at `--additive_snrs` dB, the reference's Additive; with `--reverb_rirs DIR`
 each selected clean slice is first convolved on the GPU with a room impulse response drawn from
 DIR's wavs: `--reverb_prob` is the share of items selected, `--reverb_max_taps` cuts the
-responses, `--reverb_resample` converts responses that are not 16 kHz), and under
+responses, `--reverb_resample` converts responses that are not 16 kHz; with `--distort KIND ...`
+each selected item (`--distort_prob`) is then clipped, has chunks of speech removed or is band
+limited on the GPU, one kind per item drawn from `clip chop bandlimit`: `--clip_factors`,
+`--chop_max`, `--chop_durs LO HI` and `--bandlimit_cutoffs` set the kinds' parameters, and
+'_clip' / '_chop' / '_bandlimit' is appended to the item's name), and under
 torch.distributed.run every
 rank trains on its shard of each epoch with RCCL gradient averaging.
 """
@@ -33,6 +37,16 @@ from segan_pytorch_amd.models import SEGAN, WSEGAN
 
 _FMAPS = [64, 128, 256, 512, 1024]
 _POOLS = [4, 4, 4, 4, 4]
+
+# the defaults of the --distort kinds (augment.Clip / Chop / BandLimit)
+DISTORT_KINDS = ('clip', 'chop', 'bandlimit')
+CLIP_FACTORS = (0.1, 0.2, 0.3, 0.4, 0.5)
+CHOP_MAX = 3
+CHOP_DURS = (0.05, 0.3)
+BANDLIMIT_CUTOFFS = (1000.0, 2000.0, 4000.0)
+DISTORT_SRATE = 16000
+DISTORT_ZEROS = 32          # augment.lowpass_bank: K = ceil(zeros srate / (2 fc)) taps a side
+DISTORT_MAX_K = 2048        # ops.FIR_MAX_K
 
 # (flag, kwargs) — names and defaults are the reference's (train.py:101-247)
 FLAGS = [
@@ -180,6 +194,25 @@ FLAGS = [
                                help='with --reverb_rirs: convert responses that are not 16 kHz to '
                                     '16 kHz on the GPU when they are read; without it their rate '
                                     'is ignored')),
+    ('--distort', dict(type=str, nargs='+', default=None, choices=list(DISTORT_KINDS),
+                       metavar='KIND',
+                       help='with --pcm_shard: the signal-level distortions (clip chop bandlimit) '
+                            'applied on the GPU, one per selected item drawn uniformly among '
+                            'those listed, after any reverberation and before any noise is '
+                            'mixed; \'_clip\' / \'_chop\' / \'_bandlimit\' is appended to the '
+                            'utterance name')),
+    ('--distort_prob', dict(type=float, default=1.0,
+                            help='probability that an item is distorted')),
+    ('--clip_factors', dict(type=float, nargs='+', default=list(CLIP_FACTORS),
+                            help='with --distort clip: clipping thresholds as fractions of the '
+                                 'item\'s peak, in (0, 1], drawn uniformly per item')),
+    ('--chop_max', dict(type=int, default=CHOP_MAX,
+                        help='with --distort chop: the most chunks removed from an item (1 .. 8)')),
+    ('--chop_durs', dict(type=float, nargs=2, default=list(CHOP_DURS), metavar=('LO', 'HI'),
+                         help='with --distort chop: a chunk lasts LO .. HI seconds')),
+    ('--bandlimit_cutoffs', dict(type=float, nargs='+', default=list(BANDLIMIT_CUTOFFS),
+                                 help='with --distort bandlimit: low-pass cutoffs in Hz, drawn '
+                                      'uniformly per item')),
 ]
 
 
@@ -225,6 +258,54 @@ def check_reverb_flags(opts):
     return True
 
 
+def check_distort_flags(opts):
+    """The --distort flags go together with --pcm_shard, and every sub-flag with its kind; anything
+    else exits with a message.  Host arithmetic only: nothing here touches a device."""
+    import math
+    kinds = getattr(opts, 'distort', None)
+    prob = getattr(opts, 'distort_prob', 1.0)
+    factors = list(getattr(opts, 'clip_factors', CLIP_FACTORS))
+    chop_max = getattr(opts, 'chop_max', CHOP_MAX)
+    durs = list(getattr(opts, 'chop_durs', CHOP_DURS))
+    cutoffs = list(getattr(opts, 'bandlimit_cutoffs', BANDLIMIT_CUTOFFS))
+    kinds = [] if kinds is None else list(kinds)
+    if not kinds and prob != 1.0:
+        raise SystemExit('--distort_prob needs --distort KIND [KIND ...]')
+    if 'clip' not in kinds and factors != list(CLIP_FACTORS):
+        raise SystemExit('--clip_factors needs --distort clip')
+    if 'chop' not in kinds and (chop_max != CHOP_MAX or durs != list(CHOP_DURS)):
+        raise SystemExit('--chop_max / --chop_durs need --distort chop')
+    if 'bandlimit' not in kinds and cutoffs != list(BANDLIMIT_CUTOFFS):
+        raise SystemExit('--bandlimit_cutoffs needs --distort bandlimit')
+    if not kinds:
+        return False
+    if getattr(opts, 'pcm_shard', None) is None or getattr(opts, 'synthetic', 0) > 0:
+        raise SystemExit('--distort distorts the batches of a pcm16 shard on the GPU: it is valid '
+                         'only together with --pcm_shard PREFIX')
+    if len(set(kinds)) != len(kinds):
+        raise SystemExit('--distort names a kind twice: {}'.format(' '.join(kinds)))
+    if not 0.0 <= prob <= 1.0:
+        raise SystemExit('--distort_prob must lie in 0 .. 1, got {}'.format(prob))
+    if 'clip' in kinds and (len(factors) == 0 or not all(0.0 < f <= 1.0 for f in factors)):
+        raise SystemExit('--clip_factors must lie in (0, 1], got {}'.format(factors))
+    if 'chop' in kinds:
+        if not 1 <= chop_max <= 8:
+            raise SystemExit('--chop_max must lie in 1 .. 8, got {}'.format(chop_max))
+        if not 0.0 < durs[0] <= durs[1] or round(durs[0] * DISTORT_SRATE) < 1:
+            raise SystemExit('--chop_durs needs 0 < LO <= HI seconds and at least one sample, got '
+                             '{}'.format(durs))
+    if 'bandlimit' in kinds:
+        if len(cutoffs) == 0 or not all(0.0 < fc < DISTORT_SRATE / 2.0 for fc in cutoffs):
+            raise SystemExit('--bandlimit_cutoffs must lie above 0 and below {} Hz (half the sample '
+                             'rate), got {}'.format(DISTORT_SRATE // 2, cutoffs))
+        for fc in cutoffs:
+            K = int(math.ceil(DISTORT_ZEROS * DISTORT_SRATE / (2.0 * fc)))
+            if K > DISTORT_MAX_K:
+                raise SystemExit('--bandlimit_cutoffs: {} Hz needs K = {} taps a side, more than '
+                                 '{}'.format(fc, K, DISTORT_MAX_K))
+    return True
+
+
 def build_parser():
     p = argparse.ArgumentParser(description=__doc__,
                                 formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -236,6 +317,7 @@ def build_parser():
 def main(opts):
     use_additive = check_additive_flags(opts)
     use_reverb = check_reverb_flags(opts)
+    use_distort = check_distort_flags(opts)
     if getattr(opts, 'sync_bn', False):
         os.environ['SEGAN_SYNC_BN'] = '1'
     rank, world, local = sdist.init_from_env()
@@ -306,6 +388,14 @@ def main(opts):
             from segan_pytorch_amd.augment import Reverb
             reverb = Reverb(opts.reverb_rirs, max_taps=opts.reverb_max_taps,
                             target_rate=16000 if opts.reverb_resample else None)
+        distort = None
+        if use_distort:
+            from segan_pytorch_amd import augment
+            make = {'clip': lambda: augment.Clip(opts.clip_factors),
+                    'chop': lambda: augment.Chop(opts.chop_max, opts.chop_durs, DISTORT_SRATE),
+                    'bandlimit': lambda: augment.BandLimit(opts.bandlimit_cutoffs, DISTORT_SRATE,
+                                                           DISTORT_ZEROS)}
+            distort = augment.Distort({k: make[k]() for k in opts.distort})
         dloader = PCMShardLoader(dset, opts.batch_size, opts.preemph, device, sampler=sampler,
                                  drop_last=(world > 1), num_workers=max(1, min(2, opts.num_workers)),
                                  additive=additive, additive_prob=opts.additive_prob,
@@ -314,7 +404,9 @@ def main(opts):
                                  # derived from seed + rank like the additive stream, but another
                                  # stream: the same integer would make both selections draw the
                                  # same uniforms
-                                 reverb_seed=[opts.seed + rank, 1])
+                                 reverb_seed=[opts.seed + rank, 1],
+                                 distort=distort, distort_prob=opts.distort_prob,
+                                 distort_seed=[opts.seed + rank, 2])
     else:
         dloader = DataLoader(dset, batch_size=opts.batch_size, shuffle=(sampler is None),
                              sampler=sampler, num_workers=workers, pin_memory=pin,
