@@ -14,6 +14,47 @@ import torch
 from . import ops
 
 
+def _one_wave(run, wav, **kw):
+    """What every `__call__(wav)` here does: one waveform (numpy array or tensor, any shape:
+    flattened) goes through the batched `run` (an `apply` or `mix`) as a batch of one row on the
+    device, and that row comes back as a CPU FloatTensor."""
+    if not torch.cuda.is_available():
+        raise RuntimeError('segan_pytorch_amd runs only on an MI355X (HIP) device; there is no '
+                           'CPU path')
+    if isinstance(wav, torch.Tensor):
+        wav = wav.detach().cpu().numpy()
+    x = torch.from_numpy(np.ascontiguousarray(np.asarray(wav, dtype=np.float32).reshape(1, -1)))
+    out, _ = run(x.cuda(), **kw)
+    return out[0].cpu().type(torch.FloatTensor)
+
+
+def _on_device(owner, device, build):
+    """owner._dev[device]: what `build(device)` returns, built once per device with that device
+    current.  `device` must be a HIP device; 'cuda' alone is the current one."""
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise RuntimeError('{}: segan_pytorch_amd runs only on an MI355X (HIP) device; there is no '
+                           'CPU path'.format(type(owner).__name__))
+    if device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    if device not in owner._dev:
+        with torch.cuda.device(device):
+            owner._dev[device] = build(device)
+    return owner._dev[device]
+
+
+def _draw_ids(rng, n, rows, ids, who, noun):
+    """One id in 0 .. n - 1 per row, uniform (one vectorised draw from `rng`); `ids` given are
+    checked, kept and not drawn.  `who` and `noun` name them in the message."""
+    if ids is None:
+        return rng.integers(n, size=rows).astype(np.int64)
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    if len(ids) != rows or (ids < 0).any() or (ids >= n).any():
+        raise ValueError('{}: {} {} in 0 .. {} expected, got {}'.format(who, rows, noun, n - 1,
+                                                                         ids.tolist()))
+    return ids
+
+
 class NoiseBank(object):
     """Noise recordings concatenated into one flat fp32 array with per-file offsets; the device
     copy is made on first use.  `NoiseBank(list_of_arrays)` takes float arrays as they are and
@@ -69,15 +110,7 @@ class NoiseBank(object):
 
     def data(self, device):
         """The flat bank on `device` (a HIP device; uploaded once per device)."""
-        device = torch.device(device)
-        if device.type != 'cuda':
-            raise RuntimeError('NoiseBank: segan_pytorch_amd runs only on an MI355X (HIP) device; '
-                               'there is no CPU path')
-        if device.index is None:
-            device = torch.device('cuda', torch.cuda.current_device())
-        if device not in self._dev:
-            self._dev[device] = torch.from_numpy(self.host).to(device)
-        return self._dev[device]
+        return _on_device(self, device, lambda dev: torch.from_numpy(self.host).to(dev))
 
     def draw(self, rng, sig_lengths, snr_levels, noise_ids=None, snrs=None, starts=None):
         """Per row, from the numpy Generator `rng`: a noise file (uniform), an SNR level (uniform
@@ -90,13 +123,7 @@ class NoiseBank(object):
         rows = len(sig_lengths)
         if starts is not None and noise_ids is None:
             raise ValueError('Additive: starts are offsets into a noise file; pass noise_ids too')
-        if noise_ids is None:
-            ids = rng.integers(len(self), size=rows)
-        else:
-            ids = np.asarray(noise_ids, dtype=np.int64).reshape(-1)
-            if len(ids) != rows or (ids < 0).any() or (ids >= len(self)).any():
-                raise ValueError('Additive: {} noise ids in 0 .. {} expected, got {}'.format(
-                    rows, len(self) - 1, ids.tolist()))
+        ids = _draw_ids(rng, len(self), rows, noise_ids, 'Additive', 'noise ids')
         if snrs is None:
             sn = np.asarray(snr_levels, dtype=np.float64)[rng.integers(len(snr_levels), size=rows)]
         else:
@@ -117,7 +144,7 @@ class NoiseBank(object):
                 r = 0 if len(st) != rows else int(np.nonzero((st < 1) | (st > limit))[0][0])
                 raise ValueError('Additive: start {} outside 1 .. {} of noise {}'.format(
                     st[r] if len(st) == rows else st.tolist(), limit[r], self.files[ids[r]]))
-        return ids.astype(np.int64), sn, st.astype(np.int64)
+        return ids, sn, st.astype(np.int64)
 
 
 class Additive(object):
@@ -183,14 +210,7 @@ class Additive(object):
         """Add noise to one clean waveform (numpy array or tensor, any shape: flattened)."""
         if nbits != 16:
             raise NotImplementedError('Additive: nbits={} is not supported (16 only)'.format(nbits))
-        if not torch.cuda.is_available():
-            raise RuntimeError('segan_pytorch_amd runs only on an MI355X (HIP) device; there is no '
-                               'CPU path')
-        if isinstance(wav, torch.Tensor):
-            wav = wav.detach().cpu().numpy()
-        x = torch.from_numpy(np.ascontiguousarray(np.asarray(wav, dtype=np.float32).reshape(1, -1)))
-        noisy, _ = self.mix(x.cuda(), srate=srate)
-        return noisy[0].cpu().type(torch.FloatTensor)
+        return _one_wave(self.mix, wav, srate=srate)
 
 
 class RIRBank(object):
@@ -286,20 +306,14 @@ class RIRBank(object):
 
     def data(self, device):
         """`ops.ReverbBankData` of the bank on `device` (a HIP device; built once per device)."""
-        device = torch.device(device)
-        if device.type != 'cuda':
-            raise RuntimeError('RIRBank: segan_pytorch_amd runs only on an MI355X (HIP) device; '
-                               'there is no CPU path')
-        if device.index is None:
-            device = torch.device('cuda', torch.cuda.current_device())
-        if device not in self._dev:
-            with torch.cuda.device(device):
-                H = ops.reverb_bank(torch.from_numpy(self.padded()).to(device))
-                table = np.stack([self.offsets[:-1], self.partitions, self.taps, self.delays], axis=1)
-                table = torch.from_numpy(np.ascontiguousarray(table, dtype=np.int32)).to(device)
-                torch.cuda.current_stream(device).synchronize()      # other streams use it next
-            self._dev[device] = ops.ReverbBankData(H, table, int(self.delays.max()))
-        return self._dev[device]
+        def build(dev):
+            H = ops.reverb_bank(torch.from_numpy(self.padded()).to(dev))
+            table = np.stack([self.offsets[:-1], self.partitions, self.taps, self.delays], axis=1)
+            table = torch.from_numpy(np.ascontiguousarray(table, dtype=np.int32)).to(dev)
+            torch.cuda.current_stream(dev).synchronize()      # other streams use it next
+            return ops.ReverbBankData(H, table, int(self.delays.max()))
+
+        return _on_device(self, device, build)
 
 
 class Reverb(object):
@@ -322,13 +336,7 @@ class Reverb(object):
         self.rng = np.random.default_rng(seed)
 
     def draw(self, rng, rows, rir_ids=None):
-        if rir_ids is None:
-            return rng.integers(len(self.bank), size=rows).astype(np.int64)
-        ids = np.asarray(rir_ids, dtype=np.int64).reshape(-1)
-        if len(ids) != rows or (ids < 0).any() or (ids >= len(self.bank)).any():
-            raise ValueError('Reverb: {} rir ids in 0 .. {} expected, got {}'.format(
-                rows, len(self.bank) - 1, ids.tolist()))
-        return ids
+        return _draw_ids(rng, len(self.bank), rows, rir_ids, 'Reverb', 'rir ids')
 
     def apply(self, clean, generator=None, rir_ids=None, lengths=None, prev=None):
         """clean [B, T] (fp32 CUDA) -> (wet [B, T], info).  `generator`: a numpy Generator used
@@ -343,14 +351,7 @@ class Reverb(object):
 
     def __call__(self, wav):
         """Reverberate one waveform (numpy array or tensor, any shape: flattened)."""
-        if not torch.cuda.is_available():
-            raise RuntimeError('segan_pytorch_amd runs only on an MI355X (HIP) device; there is no '
-                               'CPU path')
-        if isinstance(wav, torch.Tensor):
-            wav = wav.detach().cpu().numpy()
-        x = torch.from_numpy(np.ascontiguousarray(np.asarray(wav, dtype=np.float32).reshape(1, -1)))
-        wet, _ = self.apply(x.cuda())
-        return wet[0].cpu().type(torch.FloatTensor)
+        return _one_wave(self.apply, wav)
 
 
 # ---------------------------------------------------------------------------------
@@ -360,27 +361,13 @@ class Reverb(object):
 DISTORT_KINDS = ('clip', 'chop', 'bandlimit')
 
 
-def _no_cpu():
-    if not torch.cuda.is_available():
-        raise RuntimeError('segan_pytorch_amd runs only on an MI355X (HIP) device; there is no '
-                           'CPU path')
-
-
-def _one_wave(wav):
-    if isinstance(wav, torch.Tensor):
-        wav = wav.detach().cpu().numpy()
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(wav, dtype=np.float32).reshape(1, -1)))
-
-
 class _RowDistortion(object):
     """What Clip, Chop and BandLimit share: draws from a numpy Generator owned by the object
     (`seed`), and `__call__(wav)` on one waveform (numpy array or tensor, any shape: flattened),
     which returns a CPU FloatTensor like `Reverb.__call__`."""
 
     def __call__(self, wav):
-        _no_cpu()
-        out, _ = self.apply(_one_wave(wav).cuda())
-        return out[0].cpu().type(torch.FloatTensor)
+        return _one_wave(self.apply, wav)
 
 
 class Clip(_RowDistortion):
@@ -505,27 +492,15 @@ class BandLimit(_RowDistortion):
 
     def data(self, device):
         """(bank, K) on `device` (a HIP device; uploaded once per device)."""
-        device = torch.device(device)
-        if device.type != 'cuda':
-            raise RuntimeError('BandLimit: segan_pytorch_amd runs only on an MI355X (HIP) device; '
-                               'there is no CPU path')
-        if device.index is None:
-            device = torch.device('cuda', torch.cuda.current_device())
-        if device not in self._dev:
-            with torch.cuda.device(device):
-                pair = (torch.from_numpy(self.bank).to(device), torch.from_numpy(self.K).to(device))
-                torch.cuda.current_stream(device).synchronize()      # other streams use it next
-            self._dev[device] = pair
-        return self._dev[device]
+        def build(dev):
+            pair = (torch.from_numpy(self.bank).to(dev), torch.from_numpy(self.K).to(dev))
+            torch.cuda.current_stream(dev).synchronize()      # other streams use it next
+            return pair
+
+        return _on_device(self, device, build)
 
     def draw(self, rng, rows, ids=None):
-        if ids is None:
-            return rng.integers(len(self.cutoffs), size=rows).astype(np.int64)
-        ids = np.asarray(ids, dtype=np.int64).reshape(-1)
-        if len(ids) != rows or (ids < 0).any() or (ids >= len(self.cutoffs)).any():
-            raise ValueError('BandLimit: {} filter ids in 0 .. {} expected, got {}'.format(
-                rows, len(self.cutoffs) - 1, ids.tolist()))
-        return ids
+        return _draw_ids(rng, len(self.cutoffs), rows, ids, 'BandLimit', 'filter ids')
 
     def apply(self, wave, generator=None, ids=None, lengths=None, prev=None, out_dtype=None):
         """wave [B, T] (fp32 CUDA) -> (filtered [B, T], info).  `ids` (per row) replaces the draw.
@@ -570,12 +545,6 @@ class Distort(object):
     def draw_kinds(self, rng, rows):
         return rng.integers(len(self.enabled), size=rows)
 
-    @staticmethod
-    def _index(a, device):
-        # pinned staging, asynchronous copy (see ops.additive_mix)
-        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).pin_memory().to(
-            device, non_blocking=True)
-
     def apply(self, wave, generator=None, prev=None, lengths=None):
         """wave [B, T] (fp32 CUDA) -> (out [B, T], info).  prev (optional fp32 CUDA [B]): the
         sample preceding each row (zeros without it); lengths: host integers.  info: kinds (numpy
@@ -607,7 +576,7 @@ class Distort(object):
                 if out is None:
                     out, prev_out = torch.empty_like(wave), torch.empty_like(prev)
                     status = torch.empty(rows, device=wave.device, dtype=torch.int32)
-                idx_d = self._index(idx, wave.device)
+                idx_d = ops._upload(torch.from_numpy(idx), wave.device)
                 y, sub = self.ops[name].apply(wave.index_select(0, idx_d), generator=rng,
                                               prev=prev.index_select(0, idx_d), lengths=sub_len)
                 out.index_copy_(0, idx_d, y)
@@ -620,9 +589,7 @@ class Distort(object):
 
     def __call__(self, wav):
         """Distort one waveform (numpy array or tensor, any shape: flattened)."""
-        _no_cpu()
-        out, _ = self.apply(_one_wave(wav).cuda())
-        return out[0].cpu().type(torch.FloatTensor)
+        return _one_wave(self.apply, wav)
 
 
 class ComposeAdditive(object):

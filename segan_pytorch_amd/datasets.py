@@ -278,6 +278,25 @@ class _BatchIndexDataset(Dataset):
         return self.shard.gather(indices)
 
 
+# The on-the-fly augmentations of `PCMShardLoader`, in the order they run.  Per stage: its name
+# (the loader's keyword and attribute prefix), the method of its object that transforms a batch of
+# waves, whether the sample preceding a slice that starts its wav is zeroed before the transform
+# sees it, and the key of the transform's output in the stage's records.
+_STAGES = (
+    # augment.Reverb: the wave convolved with a drawn RIR, as if silence
+    # preceded the slice; the preceding sample takes part, so it is zero at the start of a wav
+    ('reverb', 'apply', True, 'wet'),
+    # augment.Distort (section 17): clipping, chunk removal or band limiting, the kind drawn per
+    # item and appended to its name; the preceding sample is clamped / kept / filtered with the row
+    ('distort', 'apply', True, 'out'),
+    # augment.Additive (section 11): noise at a drawn SNR; the P.56 level, the noise power and the
+    # clipping test are taken over the T samples at 16 kHz, the segment starts at s >= 1 of its
+    # file.  Alone it takes the stored preceding sample as it is: `ops.preemph_rows` ignores it
+    # where the slice starts its wav
+    ('additive', 'mix', False, 'mixed'),
+)
+
+
 class PCMShardLoader(object):
     """The full-rate input pipeline of `train.py --pcm_shard`: whole
     batches are gathered from the int16 shard by DataLoader WORKER processes (one vectorised
@@ -294,21 +313,18 @@ class PCMShardLoader(object):
                  record_reverb=False, distort=None, distort_prob=1.0, distort_seed=None,
                  record_distort=False):
         from torch.utils.data import RandomSampler
-        if additive is not None and not 0.0 <= float(additive_prob) <= 1.0:
-            raise ValueError('additive_prob must lie in 0 .. 1, got {}'.format(additive_prob))
-        self.additive, self.additive_prob = additive, float(additive_prob)
-        self.additive_rng = np.random.default_rng(additive_seed)
-        self.additive_records = [] if record_additive else None
-        if reverb is not None and not 0.0 <= float(reverb_prob) <= 1.0:
-            raise ValueError('reverb_prob must lie in 0 .. 1, got {}'.format(reverb_prob))
-        self.reverb, self.reverb_prob = reverb, float(reverb_prob)
-        self.reverb_rng = np.random.default_rng(reverb_seed)      # its own stream of draws
-        self.reverb_records = [] if record_reverb else None
-        if distort is not None and not 0.0 <= float(distort_prob) <= 1.0:
-            raise ValueError('distort_prob must lie in 0 .. 1, got {}'.format(distort_prob))
-        self.distort, self.distort_prob = distort, float(distort_prob)
-        self.distort_rng = np.random.default_rng(distort_seed)     # a third stream of draws
-        self.distort_records = [] if record_distort else None
+        # per stage of _STAGES: self.<stage>, <stage>_prob, <stage>_rng (its own stream of draws)
+        # and <stage>_records
+        for stage, obj, prob, seed, record in (
+                ('additive', additive, additive_prob, additive_seed, record_additive),
+                ('reverb', reverb, reverb_prob, reverb_seed, record_reverb),
+                ('distort', distort, distort_prob, distort_seed, record_distort)):
+            if obj is not None and not 0.0 <= float(prob) <= 1.0:
+                raise ValueError('{}_prob must lie in 0 .. 1, got {}'.format(stage, prob))
+            setattr(self, stage, obj)
+            setattr(self, stage + '_prob', float(prob))
+            setattr(self, stage + '_rng', np.random.default_rng(seed))
+            setattr(self, stage + '_records', [] if record else None)
         self.shard = shard
         self.sampler = sampler if sampler is not None else RandomSampler(shard)
         self.preemph = float(preemph)
@@ -336,141 +352,91 @@ class PCMShardLoader(object):
         pcm_d = pcm.to(self.device, non_blocking=True)
         first_d = first.to(self.device, non_blocking=True)
         clean, noisy = ops.pcm16_prep(pcm_d, first_d, self.preemph)
-        wet = None
-        if self.reverb is not None:
-            names, wet = self._reverberate(names, pcm_d, first_d, noisy)
-        if self.distort is not None:
-            names, wet = self._distort(names, pcm_d, first_d, noisy, wet)
-        if self.additive is not None:
-            names = self._add_noise(names, pcm_d, first_d, noisy, wet)
+        enabled = [st for st in _STAGES if getattr(self, st[0]) is not None]
+        done = None
+        for st in enabled:
+            names, done = self._run_stage(st, names, pcm_d, first_d, noisy, done,
+                                          last=st is enabled[-1])
         return [names, clean, noisy, idx]
 
     def _index_to_device(self, a):
-        # pinned staging and an asynchronous copy: a pageable copy would hold the host until the
-        # batch copy queued before it on this stream has finished
-        t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64))
-        if self.device.type == 'cuda':
-            t = t.pin_memory()
-        return t.to(self.device, non_blocking=True)
-
-    def _reverberate(self, names, pcm_d, first_d, noisy):
-        """On-the-fly reverberation (augment.Reverb), before any noise is
-        mixed: each item is selected with probability `reverb_prob` from the loader's own reverb
-        generator (the additive draws are the same with and without reverb).  A selected item's
-        wave is the fp32 min-max-normalised clean slice, convolved with a drawn RIR; the sample
-        preceding the slice takes part (zero where the slice starts its wav) and its reverberant
-        value is what the pre-emphasis of the row uses.  The noisy row becomes the pre-emphasised
-        reverberant wave — or, where the item is also selected for `additive`, `_add_noise` mixes
-        noise into the reverberant wave first.  '_reverb' is appended to the name; `clean` is
-        untouched.  Returns (names, (selected items, wet [n, T], wet prev [n]) or None)."""
+        # pinned and asynchronous: a pageable copy would hold the host until the batch copy queued
+        # before it on this stream has finished
         from . import ops
-        B, T = noisy.shape
-        sel = np.nonzero(self.reverb_rng.random(B) < self.reverb_prob)[0]
-        if len(sel) == 0:
-            if self.reverb_records is not None:
-                self.reverb_records.append(None)
-            return names, None
-        wave, prev = ops.pcm16_wave(pcm_d, sel)
-        sel_d = self._index_to_device(sel)
-        prev = prev.masked_fill(first_d.index_select(0, sel_d) != 0, 0.0)   # nothing precedes a wav
-        wet, info = self.reverb.apply(wave, generator=self.reverb_rng, prev=prev)
-        ops.preemph_rows(wet, info['prev'], first_d, noisy, self.preemph, sel)
-        if self.reverb_records is not None:
-            info.update(index=sel, wave=wave, wave_prev=prev, wet=wet)
-            self.reverb_records.append(info)
-        chosen = set(sel.tolist())
-        return ([n + '_reverb' if i in chosen else n for i, n in enumerate(names)],
-                (sel, wet, info['prev']))
+        return ops._upload(torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)), self.device)
 
-    def _replace_rows(self, sel, wave, prev, done):
-        """wave [n, T] / prev [n] of the items `sel`, with the rows of items that an earlier stage
-        has already replaced (`done` = (items, waves, prevs), or None) copied over them."""
-        if done is None:
-            return
-        dsel, dwave, dprev = done
-        both, ia, ir = np.intersect1d(sel, dsel, assume_unique=True, return_indices=True)
-        if len(both):
-            ix = self._index_to_device(np.stack([ia, ir]))
-            wave.index_copy_(0, ix[0], dwave.index_select(0, ix[1]))
-            prev.index_copy_(0, ix[0], dprev.index_select(0, ix[1]))
+    def _run_stage(self, st, names, pcm_d, first_d, noisy, done, last):
+        """One on-the-fly augmentation (a row of `_STAGES`) on one batch.  Runs on the stream `_prep`
+        runs on (the loader's side stream), between the H2D copy and the consumer.
 
-    def _distort(self, names, pcm_d, first_d, noisy, done):
-        """On-the-fly clipping, chunk removal or band limiting (augment.Distort, DESIGN.md section
-        17), after the reverberation and before any noise is mixed: each item is selected with
-        probability `distort_prob` from the loader's own distort generator, a third stream (the
-        reverb and additive selections and draws are the same with and without it).  A selected
-        item's wave is its reverberant wave if `_reverberate` selected it, else the fp32 min-max-
-        normalised clean slice; the sample preceding the slice is carried the same way (zero where
-        the slice starts its wav, the reverberant one after reverb).  The noisy row becomes the
-        pre-emphasised distorted wave — or, where the item is also selected for `additive`,
-        `_add_noise` mixes noise into the distorted wave first.  '_clip', '_chop' or '_bandlimit'
-        is appended to the name; `clean` is untouched.  `done`: the rows replaced so far (what
-        `_reverberate` returned); returns (names, done with this stage's rows merged in)."""
+        Each item is selected with probability `<stage>_prob` from the stage's own generator, and
+        the transform draws from the same generator after that: one stage's selections and draws
+        are the same whichever other stages are on.  An empty selection is recorded as None and
+        nothing else happens.
+
+        A selected item's wave is the fp32 min-max-normalised clean slice of T samples, with the
+        sample preceding the slice beside it (`ops.pcm16_wave`) - or, for an item that an earlier
+        stage replaced (`done`: items ascending, waves [n, T], prevs [n]), that stage's wave and
+        preceding sample.  So levels, scale factors, thresholds and filters are taken on the wave
+        as the stages before left it: noise is mixed into the reverberant or distorted wave.  Where
+        the table says so, the preceding sample is zero where the slice starts its wav (nothing
+        precedes a wav).
+
+        The transform returns the new wave and, as info['prev'], the preceding sample as it has
+        transformed it (the reverberant, clamped or filtered one; clean_prev + sf * noise[s-1]
+        followed by the slice's own anti-clipping divisions, rounded to fp32).  The pre-emphasis
+        needs that one, not the stored one: y[0] = x[0] - coef * x[-1] must see the same signal on
+        both sides of the slice's edge (y[0] = x[0] where the slice starts its wav).  It is computed
+        in double and rounded once, like the unaugmented rows (`ops.preemph_rows`), and replaces
+        the item's noisy row.  `clean` is never touched: it stays the regression target.  The
+        stage's suffix is appended to the item's name: the stage's name, or the row's own kind
+        where the transform reports `kinds` (WSEGAN's masked regression term applies to exactly
+        the '_additive' items).
+
+        Returns (names, done): `done` with this stage's rows merged in - its own rows plus the
+        earlier rows it did not select, sorted by item - or None from the `last` enabled stage,
+        after which nobody reads it."""
         from . import ops
-        B, T = noisy.shape
-        sel = np.nonzero(self.distort_rng.random(B) < self.distort_prob)[0]
+        stage, method, zero_first, out_key = st
+        rng, records = getattr(self, stage + '_rng'), getattr(self, stage + '_records')
+        sel = np.nonzero(rng.random(noisy.shape[0]) < getattr(self, stage + '_prob'))[0]
         if len(sel) == 0:
-            if self.distort_records is not None:
-                self.distort_records.append(None)
+            if records is not None:
+                records.append(None)
             return names, done
         wave, prev = ops.pcm16_wave(pcm_d, sel)
-        sel_d = self._index_to_device(sel)
-        prev = prev.masked_fill(first_d.index_select(0, sel_d) != 0, 0.0)   # nothing precedes a wav
-        self._replace_rows(sel, wave, prev, done)
-        out, info = self.distort.apply(wave, generator=self.distort_rng, prev=prev)
-        ops.preemph_rows(out, info['prev'], first_d, noisy, self.preemph, sel)
-        if self.distort_records is not None:
-            info.update(index=sel, wave=wave, wave_prev=prev, out=out)
-            self.distort_records.append(info)
-        kind = dict(zip(sel.tolist(), info['kinds']))
-        names = [n + '_' + kind[i] if i in kind else n for i, n in enumerate(names)]
+        if zero_first:
+            sel_d = self._index_to_device(sel)
+            prev = prev.masked_fill(first_d.index_select(0, sel_d) != 0, 0.0)
         if done is not None:
-            # the earlier stage's rows that this one did not touch stay what they are
             dsel, dwave, dprev = done
+            both, ia, ir = np.intersect1d(sel, dsel, assume_unique=True, return_indices=True)
+            if len(both):
+                ix = self._index_to_device(np.stack([ia, ir]))
+                wave.index_copy_(0, ix[0], dwave.index_select(0, ix[1]))
+                prev.index_copy_(0, ix[0], dprev.index_select(0, ix[1]))
+        out, info = getattr(getattr(self, stage), method)(wave, generator=rng, prev=prev)
+        ops.preemph_rows(out, info['prev'], first_d, noisy, self.preemph, sel)
+        if records is not None:
+            info.update({'index': sel, 'wave': wave, 'wave_prev': prev, out_key: out})
+            records.append(info)
+        suffix = dict(zip(sel.tolist(), info.get('kinds', [stage] * len(sel))))
+        names = [n + '_' + suffix[i] if i in suffix else n for i, n in enumerate(names)]
+        if last:
+            return names, None
+        oprev = info['prev']
+        if done is not None:
+            # the earlier stages' rows that this one did not select stay what they are
             keep = np.nonzero(~np.isin(dsel, sel))[0]
             if len(keep):
                 keep_d = self._index_to_device(keep)
-                items = np.concatenate((sel, dsel[keep]))
-                order = np.argsort(items, kind='stable')
+                sel = np.concatenate((sel, dsel[keep]))
+                order = np.argsort(sel, kind='stable')
                 order_d = self._index_to_device(order)
                 out = torch.cat((out, dwave.index_select(0, keep_d))).index_select(0, order_d)
-                oprev = torch.cat((info['prev'], dprev.index_select(0, keep_d))).index_select(
-                    0, order_d)
-                return names, (items[order], out, oprev)
-        return names, (sel, out, info['prev'])
-
-    def _add_noise(self, names, pcm_d, first_d, noisy, wet=None):
-        """On-the-fly additive noise (augment.Additive): each item is
-        selected with probability `additive_prob`; a selected item's noisy row becomes clean +
-        noise and its name gets '_additive' appended (WSEGAN's masked regression term applies to
-        exactly those).  Per selected slice: the wave is the fp32 min-max-normalised clean slice
-        of T samples; the P.56 level, the noise power and the clipping test are taken over those T
-        samples, at 16 kHz; the noise segment starts at s >= 1 of its file.  When the slice does not start
-        its wav, the pre-emphasis of the mixed row needs the sample preceding the slice: it is
-        (clean_prev + sf * noise[s-1]) followed by the slice's own anti-clipping divisions,
-        rounded to fp32; when it does, y[0] = x[0].  The pre-emphasis is computed in double and
-        rounded once, like the unaugmented rows.  Runs on the stream `_prep` runs on (the
-        loader's side stream), between the H2D copy and the consumer; `clean` is untouched.
-        `wet`: the rows that `_reverberate` / `_distort` have already replaced, with their prev:
-        the wave of such an item is its reverberant / distorted wave."""
-        from . import ops
-        B, T = noisy.shape
-        sel = np.nonzero(self.additive_rng.random(B) < self.additive_prob)[0]
-        if len(sel) == 0:
-            if self.additive_records is not None:
-                self.additive_records.append(None)
-            return names
-        wave, prev = ops.pcm16_wave(pcm_d, sel)
-        # items that were reverberated or distorted: the level, sf and the divisions are taken on
-        # that wave, and the sample before the slice is that wave's
-        self._replace_rows(sel, wave, prev, wet)
-        mixed, info = self.additive.mix(wave, generator=self.additive_rng, prev=prev)
-        ops.preemph_rows(mixed, info['prev'], first_d, noisy, self.preemph, sel)
-        if self.additive_records is not None:
-            info.update(index=sel, wave=wave, wave_prev=prev, mixed=mixed)
-            self.additive_records.append(info)
-        chosen = set(sel.tolist())
-        return [n + '_additive' if i in chosen else n for i, n in enumerate(names)]
+                oprev = torch.cat((oprev, dprev.index_select(0, keep_d))).index_select(0, order_d)
+                sel = sel[order]
+        return names, (sel, out, oprev)
 
     def _stage(self, item):
         """H2D copy + prep kernel of one batch on the loader's SIDE stream; (batch, event)."""

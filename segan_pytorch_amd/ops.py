@@ -108,15 +108,15 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
-def _chk(t, name, ndim=None):
+def _chk(t, name, ndim=None, dtype=torch.float32):
     if not isinstance(t, torch.Tensor):
         raise TypeError('{} must be a tensor, got {}'.format(name, type(t)))
     if not t.is_cuda:
         raise RuntimeError(
             '{} is on {}: segan_pytorch_amd runs only on an MI355X (HIP) device; '
             'there is no CPU path'.format(name, t.device))
-    if t.dtype != torch.float32:
-        raise TypeError('{} must be float32, got {}'.format(name, t.dtype))
+    if t.dtype != dtype:
+        raise TypeError('{} must be {}, got {}'.format(name, str(dtype)[len('torch.'):], t.dtype))
     if not t.is_contiguous():
         raise ValueError('{} must be contiguous'.format(name))
     if ndim is not None and t.dim() != ndim:
@@ -1099,7 +1099,14 @@ def stoi_plan(srate):
     return p, q, taps, torch.tensor(list(bands), dtype=torch.int64).view(STOI_BANDS, 2)
 
 
-def _row_lengths(what, lengths, rows, T, device):
+def _row_lengths(what, lengths, rows, T, device, device_ok=False):
+    """Host integers [rows], checked to lie in 0 .. T, as an int32 tensor on `device`.  With
+    `device_ok`, a CUDA tensor is used as it is (int32 [rows] on `device`; its values are left to
+    the kernel) and nothing is copied to the host."""
+    if device_ok and isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+        if lengths.dtype != torch.int32 or lengths.shape != (rows,) or lengths.device != device:
+            raise ValueError('{}: device lengths must be int32 [{}] on {}'.format(what, rows, device))
+        return lengths.contiguous()
     lens = torch.as_tensor(lengths).detach().cpu()
     if lens.dim() != 1 or lens.numel() != rows or lens.dtype.is_floating_point or lens.dtype in (
             torch.bool, torch.complex64, torch.complex128):
@@ -1463,13 +1470,66 @@ def asl_p56(x, srate=16000, nbits=16, lengths=None):
     return asl_p56_stages(x, srate, nbits, lengths, _want_q=False)
 
 
-def _host_vec(v, rows, dtype, what):
-    t = torch.as_tensor(v).detach().cpu().reshape(-1)
-    if t.numel() != rows:
-        raise ValueError('additive_mix: {} must hold {} values, got {}'.format(what, rows, t.numel()))
-    if dtype == torch.int64 and (t.dtype.is_floating_point or t.dtype == torch.bool):
-        raise ValueError('additive_mix: {} must be integers'.format(what))
-    return t.to(dtype)
+def _upload(t, device):
+    """The host tensor t on `device`, through pinned staging in an asynchronous copy: a pageable
+    copy would hold the host until everything queued on this stream before it (the loader's 20 MB
+    batch copy) has finished.  Pinned only when the target is a HIP device."""
+    if torch.device(device).type == 'cuda':
+        t = t.pin_memory()
+    return t.to(device, non_blocking=True)
+
+
+def _host_rows(what, name, v, shape, dtype, check_host=None):
+    """Per-row host values as a contiguous CPU tensor of `dtype` and `shape`; `check_host` sees
+    them in their own dtype first."""
+    # through numpy: python floats stay float64 (torch.as_tensor would make them float32)
+    t = v.detach().cpu() if isinstance(v, torch.Tensor) else torch.from_numpy(np.asarray(v))
+    n = 1
+    for s in shape:
+        n *= s
+    if t.numel() != n or t.dtype in (torch.bool, torch.complex64, torch.complex128):
+        raise ValueError('{}: {} must hold {} values, got {}'.format(
+            what, name, ' x '.join(str(s) for s in shape), list(t.shape)))
+    if not dtype.is_floating_point and t.dtype.is_floating_point:
+        raise ValueError('{}: {} must be integers'.format(what, name))
+    t = t.reshape(shape)
+    if check_host is not None:
+        check_host(t)
+    return t.to(dtype).contiguous()
+
+
+def _row_arg(what, name, v, shape, dtype, device, check_host=None):
+    """A per-row argument on `device`: a CUDA tensor of `dtype` and `shape` is used as it is (its
+    values are the caller's business: the kernels flag what they cannot use); host values are
+    checked by `check_host` and uploaded (`_host_rows`, `_upload`)."""
+    if isinstance(v, torch.Tensor) and v.is_cuda:
+        if v.dtype != dtype or tuple(v.shape) != tuple(shape) or v.device != device:
+            raise ValueError('{}: device {} must be {} {} on {}, got {} {}'.format(
+                what, name, dtype, list(shape), device, v.dtype, list(v.shape)))
+        return v.contiguous()
+    return _upload(_host_rows(what, name, v, shape, dtype, check_host), device)
+
+
+def _fits_int32(what, name, t):
+    if int(t.min()) < -(1 << 31) or int(t.max()) >= 1 << 31:
+        raise ValueError('{}: {} do not fit 32 bits'.format(what, name))
+
+
+def _level_arg(what, name, t, rows):
+    """asl_ms or c0 of `asl_p56`: an fp64 CUDA tensor of one value per row.  They are columns of
+    one block there, so a strided one is taken and made contiguous (which `_chk` would refuse)."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and
+            t.numel() == rows):
+        raise TypeError('{}: {} must be a CUDA float64 tensor of {} values'.format(what, name, rows))
+    return t.contiguous()
+
+
+def _prev_arg(what, prev, rows, device):
+    """prev (the sample preceding each row), when given: fp32 [rows] on `device`."""
+    if prev is not None:
+        _chk(prev, 'prev', 1)
+        if prev.numel() != rows or prev.device != device:
+            raise ValueError('{}: prev must hold {} values on {}'.format(what, rows, device))
 
 
 def additive_mix(clean, bank, starts, snrs, px, lengths=None, prev=None):
@@ -1488,13 +1548,12 @@ def additive_mix(clean, bank, starts, snrs, px, lengths=None, prev=None):
     rows, T = clean.shape
     if rows == 0 or T == 0 or bank.numel() == 0:
         raise ValueError('additive_mix: empty input')
-    if not (isinstance(px, torch.Tensor) and px.is_cuda and px.dtype == torch.float64 and
-            px.numel() == rows):
-        raise TypeError('additive_mix: px must be a CUDA float64 tensor of {} values'.format(rows))
+    px = _level_arg('additive_mix', 'px', px, rows)
     if bank.device != clean.device or px.device != clean.device:
         raise ValueError('additive_mix: tensors on different devices')
-    st = _host_vec(starts, rows, torch.int64, 'starts')
-    sn = _host_vec(snrs, rows, torch.float64, 'snrs')
+    # torch.as_tensor: snrs given as python floats are float32 values, as they have always been
+    st = _host_rows('additive_mix', 'starts', torch.as_tensor(starts), (rows,), torch.int64)
+    sn = _host_rows('additive_mix', 'snrs', torch.as_tensor(snrs), (rows,), torch.float64)
     lens = None if lengths is None else _row_lengths('additive_mix', lengths, rows, T, clean.device)
     need = torch.full((rows,), T, dtype=torch.int64) if lens is None else lens.cpu().to(torch.int64)
     lo = 1 if prev is not None else 0
@@ -1503,10 +1562,7 @@ def additive_mix(clean, bank, starts, snrs, px, lengths=None, prev=None):
                          'lengths {})'.format(bank.numel(), st.tolist(), need.tolist()))
     if not bool(torch.isfinite(sn).all()):
         raise ValueError('additive_mix: snrs must be finite, got {}'.format(sn.tolist()))
-    if prev is not None:
-        _chk(prev, 'prev', 1)
-        if prev.numel() != rows:
-            raise ValueError('additive_mix: prev must hold {} values'.format(rows))
+    _prev_arg('additive_mix', prev, rows, clean.device)
     # one pinned staging buffer, one asynchronous copy: a pageable copy would hold the host until
     # everything queued on this stream before it (the loader's 20 MB batch copy) has finished
     args = torch.empty(2 * rows, dtype=torch.int64).pin_memory()
@@ -1519,7 +1575,7 @@ def additive_mix(clean, bank, starts, snrs, px, lengths=None, prev=None):
     info = torch.empty((rows, 2), device=clean.device, dtype=torch.float64)
     istat = torch.empty((rows, 2), device=clean.device, dtype=torch.int32)
     check(_lib.load().segan_additive_mix(_ptr(clean), _ptr(lens), _ptr(bank), bank.numel(),
-                                         _ptr(st_d), _ptr(sn_d), _ptr(px.contiguous()), _ptr(prev),
+                                         _ptr(st_d), _ptr(sn_d), _ptr(px), _ptr(prev),
                                          rows, T, _ptr(noisy), _ptr(prev_out), _ptr(info),
                                          _ptr(istat), _stream()), 'additive_mix')
     out = dict(Pn=info[:, 0], sf=info[:, 1], n=istat[:, 0], status=istat[:, 1])
@@ -1600,14 +1656,7 @@ def resample(x, rate_in, rate_out, lengths=None, out_dtype=None, zeros=RESAMPLE_
         raise ValueError('resample: x must be contiguous')
     rate_in, rate_out, zeros, beta = _resample_args(rate_in, rate_out, zeros, beta)
     rows, T = x.shape
-    if lengths is None:
-        lens = None
-    elif isinstance(lengths, torch.Tensor) and lengths.is_cuda:
-        if lengths.dtype != torch.int32 or lengths.shape != (rows,) or lengths.device != x.device:
-            raise ValueError('resample: device lengths must be int32 [{}] on {}'.format(rows, x.device))
-        lens = lengths.contiguous()
-    else:
-        lens = _row_lengths('resample', lengths, rows, T, x.device)
+    lens = None if lengths is None else _row_lengths('resample', lengths, rows, T, x.device, True)
     lib = _lib.load()
     dims = (ctypes.c_int * 2)()
     check(lib.segan_resample_dims(T, rate_in, rate_out, dims), 'resample')
@@ -1632,7 +1681,7 @@ def _index_arg(index, B, device, what):
         raise ValueError('{}: index must hold integers, got {}'.format(what, index))
     if int(idx.min()) < 0 or int(idx.max()) >= B:
         raise ValueError('{}: index outside 0 .. {}: {}'.format(what, B - 1, idx.tolist()))
-    return idx.to(torch.int32).pin_memory().to(device, non_blocking=True), idx.numel()
+    return _upload(idx.to(torch.int32), device), idx.numel()
 
 
 def pcm16_wave(pcm, index=None):
@@ -1738,11 +1787,9 @@ class ReverbBankData(object):
 
     def __init__(self, H, table, max_delay):
         _chk(H, 'H', 2)
-        if not (isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.int32 and
-                table.dim() == 2 and table.shape[1] == 4 and table.is_contiguous() and
-                table.shape[0] > 0 and table.device == H.device):
-            raise TypeError('ReverbBankData: table must be a contiguous CUDA int32 [n_rirs, 4] on '
-                            "H's device")
+        _chk(table, 'table', None, torch.int32)
+        if table.dim() != 2 or table.shape[1] != 4 or table.shape[0] == 0 or table.device != H.device:
+            raise TypeError("ReverbBankData: table must be int32 [n_rirs, 4] on H's device")
         if H.shape[1] != 2 * REVERB_P or H.shape[0] == 0:
             raise ValueError('ReverbBankData: H must be [n_parts, {}]'.format(2 * REVERB_P))
         self.H, self.table = H, table
@@ -1760,25 +1807,10 @@ def _reverb_args(x, bank, rir_ids, lengths, prev):
         raise TypeError('reverb_rows: bank must be an augment.RIRBank or a ReverbBankData')
     if bank.H.device != x.device:
         raise ValueError('reverb_rows: tensors on different devices')
-    if isinstance(rir_ids, torch.Tensor) and rir_ids.is_cuda:
-        ids = rir_ids
-        if ids.dtype != torch.int32 or ids.numel() != rows or not ids.is_contiguous():
-            raise ValueError('reverb_rows: device rir_ids must be contiguous int32 [{}]'.format(rows))
-    else:
-        ids = torch.as_tensor(rir_ids).detach().cpu().reshape(-1)
-        if ids.numel() != rows or ids.dtype.is_floating_point or ids.dtype == torch.bool:
-            raise ValueError('reverb_rows: rir_ids must hold {} integers, got {}'.format(
-                rows, rir_ids))
-        ids = ids.to(torch.int64)
-        if int(ids.min()) < -(1 << 31) or int(ids.max()) >= (1 << 31):
-            raise ValueError('reverb_rows: rir_ids do not fit 32 bits')
-        # pinned staging, asynchronous copy (see additive_mix)
-        ids = ids.to(torch.int32).pin_memory().to(x.device, non_blocking=True)
+    ids = _row_arg('reverb_rows', 'rir_ids', rir_ids, (rows,), torch.int32, x.device,
+                   lambda t: _fits_int32('reverb_rows', 'rir_ids', t))
     lens = None if lengths is None else _row_lengths('reverb_rows', lengths, rows, T, x.device)
-    if prev is not None:
-        _chk(prev, 'prev', 1)
-        if prev.numel() != rows:
-            raise ValueError('reverb_rows: prev must hold {} values'.format(rows))
+    _prev_arg('reverb_rows', prev, rows, x.device)
     return bank, ids, lens
 
 
@@ -1875,45 +1907,9 @@ def _distort_rows(what, x, lengths, prev):
         raise ValueError('{}: empty input {}'.format(what, tuple(x.shape)))
     if rows > DISTORT_MAX_ROWS:
         raise ValueError('{}: 1 .. {} rows, got {}'.format(what, DISTORT_MAX_ROWS, rows))
-    if lengths is None:
-        lens = None
-    elif isinstance(lengths, torch.Tensor) and lengths.is_cuda:
-        if lengths.dtype != torch.int32 or lengths.shape != (rows,) or lengths.device != x.device:
-            raise ValueError('{}: device lengths must be int32 [{}] on {}'.format(what, rows,
-                                                                                  x.device))
-        lens = lengths.contiguous()
-    else:
-        lens = _row_lengths(what, lengths, rows, T, x.device)
-    if prev is not None:
-        _chk(prev, 'prev', 1)
-        if prev.numel() != rows or prev.device != x.device:
-            raise ValueError('{}: prev must hold {} values on {}'.format(what, rows, x.device))
+    lens = None if lengths is None else _row_lengths(what, lengths, rows, T, x.device, True)
+    _prev_arg(what, prev, rows, x.device)
     return rows, T, lens
-
-
-def _distort_arg(what, name, v, shape, dtype, device, check_host=None):
-    """A per-row argument: a CUDA tensor of `dtype` and `shape` is used as it is (its values are
-    the caller's business: the kernels flag what they cannot use); host values are checked by
-    `check_host` and travel through pinned memory in an asynchronous copy (see additive_mix)."""
-    if isinstance(v, torch.Tensor) and v.is_cuda:
-        if v.dtype != dtype or tuple(v.shape) != tuple(shape) or v.device != device:
-            raise ValueError('{}: device {} must be {} {} on {}, got {} {}'.format(
-                what, name, dtype, list(shape), device, v.dtype, list(v.shape)))
-        return v.contiguous()
-    # through numpy: python floats stay float64 (torch.as_tensor would make them float32)
-    t = v.detach().cpu() if isinstance(v, torch.Tensor) else torch.from_numpy(np.asarray(v))
-    n = 1
-    for s in shape:
-        n *= s
-    if t.numel() != n or t.dtype in (torch.bool, torch.complex64, torch.complex128):
-        raise ValueError('{}: {} must hold {} values, got {}'.format(what, name, list(shape),
-                                                                     list(t.shape)))
-    if not dtype.is_floating_point and t.dtype.is_floating_point:
-        raise ValueError('{}: {} must be integers'.format(what, name))
-    t = t.reshape(shape)
-    if check_host is not None:
-        check_host(t)
-    return t.to(dtype).contiguous().pin_memory().to(device, non_blocking=True)
 
 
 def clip_rows(x, factors, lengths=None, prev=None):
@@ -1933,7 +1929,7 @@ def clip_rows(x, factors, lengths=None, prev=None):
         if not bool(((f > 0) & (f <= 1)).all()):
             raise ValueError('clip_rows: factors must lie in (0, 1], got {}'.format(f.tolist()))
 
-    f_d = _distort_arg('clip_rows', 'factors', factors, (rows,), torch.float64, x.device, ok)
+    f_d = _row_arg('clip_rows', 'factors', factors, (rows,), torch.float64, x.device, ok)
     y = torch.empty_like(x)
     prev_out = torch.empty_like(prev) if prev is not None else None
     m = torch.empty(rows, device=x.device, dtype=torch.float32)
@@ -1960,13 +1956,10 @@ def chop_rows(x, q, c0, u, dur, lengths=None):
     [rows]: CHOP_NOLEVEL (c0 is NaN or nothing is active: the row unchanged, every start -1)).
     Integer arithmetic throughout; no device-to-host copy."""
     rows, T, lens = _distort_rows('chop_rows', x, lengths, None)
-    if not (isinstance(q, torch.Tensor) and q.is_cuda and q.dtype == torch.float64 and
-            tuple(q.shape) == (rows, T) and q.is_contiguous()):
-        raise TypeError('chop_rows: q must be a contiguous CUDA float64 tensor [{}, {}]'.format(
-            rows, T))
-    if not (isinstance(c0, torch.Tensor) and c0.is_cuda and c0.dtype == torch.float64 and
-            c0.numel() == rows):
-        raise TypeError('chop_rows: c0 must be a CUDA float64 tensor of {} values'.format(rows))
+    _chk(q, 'q', None, torch.float64)
+    if tuple(q.shape) != (rows, T):
+        raise TypeError('chop_rows: q must be float64 [{}, {}]'.format(rows, T))
+    c0 = _level_arg('chop_rows', 'c0', c0, rows)
     if q.device != x.device or c0.device != x.device:
         raise ValueError('chop_rows: tensors on different devices')
     ushape = tuple(u.shape) if hasattr(u, 'shape') else tuple(torch.as_tensor(u).shape)
@@ -1984,14 +1977,14 @@ def chop_rows(x, q, c0, u, dur, lengths=None):
         if int(t.min()) < 0 or int(t.max()) >= 1 << 31:
             raise ValueError('chop_rows: dur must lie in 0 .. 2^31 - 1, got {}'.format(t.tolist()))
 
-    u_d = _distort_arg('chop_rows', 'u', u, (rows, C), torch.float64, x.device, u_ok)
-    d_d = _distort_arg('chop_rows', 'dur', dur, (rows, C), torch.int32, x.device, dur_ok)
+    u_d = _row_arg('chop_rows', 'u', u, (rows, C), torch.float64, x.device, u_ok)
+    d_d = _row_arg('chop_rows', 'dur', dur, (rows, C), torch.int32, x.device, dur_ok)
     y = torch.empty_like(x)
     starts = torch.empty((rows, C), device=x.device, dtype=torch.int32)
     nact = torch.empty(rows, device=x.device, dtype=torch.int32)
     nzero = torch.empty(rows, device=x.device, dtype=torch.int32)
     status = torch.empty(rows, device=x.device, dtype=torch.int32)
-    check(_lib.load().segan_chop_rows(_ptr(x), _ptr(lens), _ptr(q), _ptr(c0.contiguous()),
+    check(_lib.load().segan_chop_rows(_ptr(x), _ptr(lens), _ptr(q), _ptr(c0),
                                       _ptr(u_d), _ptr(d_d), rows, T, C, _ptr(y), _ptr(starts),
                                       _ptr(nact), _ptr(nzero), _ptr(status), _stream()),
           'chop_rows')
@@ -2013,23 +2006,19 @@ def fir_rows(x, bank, K, ids, lengths=None, prev=None, out_dtype=None):
     if out_dtype not in (torch.float32, torch.float64):
         raise TypeError('fir_rows: out_dtype must be torch.float32 or torch.float64, got {}'.format(
             out_dtype))
-    if not (isinstance(bank, torch.Tensor) and bank.is_cuda and bank.dtype == torch.float64 and
-            bank.dim() == 2 and bank.is_contiguous() and bank.shape[0] > 0 and bank.shape[1] > 0):
-        raise TypeError('fir_rows: bank must be a contiguous CUDA float64 tensor [nf, Kmax + 1]')
+    _chk(bank, 'bank', None, torch.float64)
+    if bank.dim() != 2 or bank.shape[0] == 0 or bank.shape[1] == 0:
+        raise TypeError('fir_rows: bank must be float64 [nf, Kmax + 1]')
     nf, kmax = bank.shape[0], bank.shape[1] - 1
     if kmax > FIR_MAX_K:
         raise ValueError('fir_rows: Kmax = {} exceeds {}'.format(kmax, FIR_MAX_K))
-    if not (isinstance(K, torch.Tensor) and K.is_cuda and K.dtype == torch.int32 and
-            tuple(K.shape) == (nf,) and K.is_contiguous()):
-        raise TypeError('fir_rows: K must be a contiguous CUDA int32 tensor [{}]'.format(nf))
+    _chk(K, 'K', None, torch.int32)
+    if tuple(K.shape) != (nf,):
+        raise TypeError('fir_rows: K must be int32 [{}]'.format(nf))
     if bank.device != x.device or K.device != x.device:
         raise ValueError('fir_rows: tensors on different devices')
-
-    def ids_ok(t):
-        if int(t.min()) < -(1 << 31) or int(t.max()) >= 1 << 31:
-            raise ValueError('fir_rows: ids do not fit 32 bits')
-
-    ids_d = _distort_arg('fir_rows', 'ids', ids, (rows,), torch.int32, x.device, ids_ok)
+    ids_d = _row_arg('fir_rows', 'ids', ids, (rows,), torch.int32, x.device,
+                     lambda t: _fits_int32('fir_rows', 'ids', t))
     y = torch.empty((rows, T), device=x.device, dtype=out_dtype)
     prev_out = torch.empty(rows, device=x.device, dtype=out_dtype)
     status = torch.empty(rows, device=x.device, dtype=torch.int32)

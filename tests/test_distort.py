@@ -241,8 +241,6 @@ def test_distort_draws_in_the_documented_order_and_scatters(monkeypatch):
     from segan_pytorch_amd import augment as A
     from segan_pytorch_amd import ops
     monkeypatch.setattr(ops, '_chk', lambda t, name, ndim=None: t)
-    monkeypatch.setattr(A.Distort, '_index', staticmethod(
-        lambda a, device: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64))))
     real = dict(clip=A.Clip(), chop=A.Chop(), bandlimit=A.BandLimit())
     log = []
     d = A.Distort({k: _Spy(k, log, v) for k, v in real.items()})

@@ -26,6 +26,7 @@ sys.path.insert(0, os.path.join(ROOT, 'scripts'))
 import distort_oracle as D  # noqa: E402
 import make_golden_additive as GA  # noqa: E402
 import make_golden_distort as G  # noqa: E402
+import make_golden_reverb as GR  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -473,6 +474,83 @@ def test_loader_rows_recomposed_from_the_recorded_draws(shard):
                 assert torch.equal(noisy[r], py[r])
                 n_plain += 1
     assert seen == {'clip', 'chop', 'bandlimit'} and n_both >= 1, (seen, n_both, n_plain)
+
+
+def test_loader_three_stages_recomposed_from_the_recorded_draws(shard):
+    """Reverb, distortion and noise together.  Per item, from the recorded draws and through the
+    public ops on that item alone, in the loader's order: the reverberant wave, the distorted wave,
+    the noise mixed into what those left, and the pre-emphasis with the preceding sample as the
+    stages transformed it.  A batched row equals its own call bit for bit for every op involved, so
+    the loader's noisy row must equal the recomposed one exactly.  The first batch holds an item
+    that every stage selected (each takes over the rows of the one before), one with reverb and
+    noise (noise on a row that the distort stage kept from the reverb stage), one with distortion
+    alone and one with reverb and distortion."""
+    from segan_pytorch_amd import augment as A
+    from segan_pytorch_amd import ops
+    noises = A.NoiseBank(GA.noise_bank())
+    rbank = A.RIRBank([GR.rir_bank()[i] for i in (6, 10, 11, 7)])      # 300, 4099, 100, 300 taps
+    band = A.BandLimit()
+    ld = _loader(shard, reverb=A.Reverb(rbank), reverb_prob=0.6, reverb_seed=2, record_reverb=True,
+                 distort=A.Distort([A.Clip(), A.Chop(), band]), distort_prob=0.6, distort_seed=12,
+                 record_distort=True, additive=A.Additive(noises), additive_prob=0.5,
+                 additive_seed=3, record_additive=True)
+    got = _batches(ld)
+    plain = _batches(_loader(shard))
+    assert len(got) == len(plain) == 2
+    seen = []
+    for k, ((names, clean, noisy, _), (pn, pc, py, _)) in enumerate(zip(got, plain)):
+        assert torch.equal(clean, pc)
+        rr, rd, ra = ld.reverb_records[k], ld.distort_records[k], ld.additive_records[k]
+        rsel, dsel, asel = ([] if rec is None else rec['index'].tolist() for rec in (rr, rd, ra))
+        B = len(names)
+        pcm = np.stack([np.array(shard.data[4 * k + r]) for r in range(B)])
+        first = shard._first[4 * k:4 * k + B]
+        first_d = _dev(first)
+        dry = ((2.0 / 65535.0) * (pcm[:, 0].astype(np.float64) - 32767.0) + 1.0).astype(np.float32)
+        for r in range(B):
+            wave, prev = _dev(dry[r, 1:]), _scalar(0.0 if first[r] else dry[r, 0])
+            want = pn[r]
+            if r in rsel:
+                j = rsel.index(r)
+                assert torch.equal(rr['wave'][j], wave) and torch.equal(rr['wave_prev'][j], prev)
+                wet, wi = ops.reverb_rows(wave[None].contiguous(), rbank, rr['rir_ids'][j:j + 1],
+                                          None, prev[None].contiguous())
+                wave, prev = wet[0], wi['prev'][0]
+                assert torch.equal(rr['wet'][j], wave) and int(wi['status'][0]) == 0
+                want += '_reverb'
+            if r in dsel:
+                j = dsel.index(r)
+                kind = rd['kinds'][j]
+                assert torch.equal(rd['wave'][j], wave) and torch.equal(rd['wave_prev'][j], prev)
+                jj = rd[kind]['index'].tolist().index(j)
+                wave, prev, st = _redo_row(kind, rd[kind], jj, wave, prev, band)
+                assert torch.equal(rd['out'][j], wave) and int(st) == 0
+                want += '_' + kind
+            if r in asel:
+                if r not in rsel and r not in dsel:
+                    prev = _scalar(dry[r, 0])      # additive alone takes the stored sample as it is
+                j = asel.index(r)
+                assert torch.equal(ra['wave'][j], wave) and torch.equal(ra['wave_prev'][j], prev)
+                level = ops.asl_p56(wave[None].contiguous())
+                mixed, mi = ops.additive_mix(wave[None].contiguous(), noises.data('cuda'),
+                                             ra['abs_starts'][j:j + 1], ra['snrs'][j:j + 1],
+                                             level['asl_ms'], None, prev[None].contiguous())
+                wave, prev = mixed[0], mi['prev'][0]
+                assert torch.equal(ra['mixed'][j], wave)
+                want += '_additive'
+            assert names[r] == want
+            if r in rsel or r in dsel or r in asel:
+                row = torch.empty(1, T_SLICE, device='cuda')
+                ops.preemph_rows(wave[None].contiguous(), prev[None].contiguous(),
+                                 first_d[r:r + 1].contiguous(), row, 0.95)
+                assert torch.equal(noisy[r], row[0].cpu()), (k, r)
+                assert not torch.equal(noisy[r], py[r])
+            else:
+                assert torch.equal(noisy[r], py[r])
+            seen.append((r in rsel, r in dsel, r in asel))
+    # (reverb, distort, additive) of the first batch's items: the four combinations above
+    assert seen[:4] == [(True, True, True), (True, False, True), (False, True, False),
+                        (True, True, False)], seen
 
 
 def test_loader_without_distort_is_unchanged(shard):

@@ -216,6 +216,17 @@ FLAGS = [
 ]
 
 
+def _needs_pcm_shard(opts, flag, does):
+    if getattr(opts, 'pcm_shard', None) is None or getattr(opts, 'synthetic', 0) > 0:
+        raise SystemExit('{} {} the batches of a pcm16 shard on the GPU: it is valid only together '
+                         'with --pcm_shard PREFIX'.format(flag, does))
+
+
+def _prob_in_range(flag, prob):
+    if not 0.0 <= prob <= 1.0:
+        raise SystemExit('{} must lie in 0 .. 1, got {}'.format(flag, prob))
+
+
 def check_additive_flags(opts):
     """The --additive_* flags go together with --pcm_shard; anything else exits with a message."""
     noises = getattr(opts, 'additive_noises', None)
@@ -227,11 +238,8 @@ def check_additive_flags(opts):
         if getattr(opts, 'additive_resample', False):
             raise SystemExit('--additive_resample needs --additive_noises DIR')
         return False
-    if getattr(opts, 'pcm_shard', None) is None or getattr(opts, 'synthetic', 0) > 0:
-        raise SystemExit('--additive_noises mixes noise into the batches of a pcm16 shard on the '
-                         'GPU: it is valid only together with --pcm_shard PREFIX')
-    if not 0.0 <= prob <= 1.0:
-        raise SystemExit('--additive_prob must lie in 0 .. 1, got {}'.format(prob))
+    _needs_pcm_shard(opts, '--additive_noises', 'mixes noise into')
+    _prob_in_range('--additive_prob', prob)
     if len(snrs) == 0:
         raise SystemExit('--additive_snrs needs at least one level')
     return True
@@ -248,11 +256,8 @@ def check_reverb_flags(opts):
         if getattr(opts, 'reverb_resample', False):
             raise SystemExit('--reverb_resample needs --reverb_rirs DIR')
         return False
-    if getattr(opts, 'pcm_shard', None) is None or getattr(opts, 'synthetic', 0) > 0:
-        raise SystemExit('--reverb_rirs reverberates the batches of a pcm16 shard on the GPU: it '
-                         'is valid only together with --pcm_shard PREFIX')
-    if not 0.0 <= prob <= 1.0:
-        raise SystemExit('--reverb_prob must lie in 0 .. 1, got {}'.format(prob))
+    _needs_pcm_shard(opts, '--reverb_rirs', 'reverberates')
+    _prob_in_range('--reverb_prob', prob)
     if max_taps < 1:
         raise SystemExit('--reverb_max_taps must be positive, got {}'.format(max_taps))
     return True
@@ -279,13 +284,10 @@ def check_distort_flags(opts):
         raise SystemExit('--bandlimit_cutoffs needs --distort bandlimit')
     if not kinds:
         return False
-    if getattr(opts, 'pcm_shard', None) is None or getattr(opts, 'synthetic', 0) > 0:
-        raise SystemExit('--distort distorts the batches of a pcm16 shard on the GPU: it is valid '
-                         'only together with --pcm_shard PREFIX')
+    _needs_pcm_shard(opts, '--distort', 'distorts')
     if len(set(kinds)) != len(kinds):
         raise SystemExit('--distort names a kind twice: {}'.format(' '.join(kinds)))
-    if not 0.0 <= prob <= 1.0:
-        raise SystemExit('--distort_prob must lie in 0 .. 1, got {}'.format(prob))
+    _prob_in_range('--distort_prob', prob)
     if 'clip' in kinds and (len(factors) == 0 or not all(0.0 < f <= 1.0 for f in factors)):
         raise SystemExit('--clip_factors must lie in (0, 1], got {}'.format(factors))
     if 'chop' in kinds:
