@@ -362,7 +362,10 @@ int segan_snorm_bwd(const float* dw_sn, const float* w, const float* u, const fl
  * (NF = 1 + T/hop, nbins = n_fft/2+1; columns [0,nbins) real, [nbins,2nbins) imaginary) run
  * through segan_gemm.  Rows of the basis and of the spectra are `pitch` =
  * segan_stft_pitch(n_fft) floats wide (2*nbins rounded up to a multiple of 4, pad columns
- * zero) so that they are 16-byte aligned for the GEMM.  Requires n_fft/2 < T. */
+ * zero) so that they are 16-byte aligned for the GEMM.  Requires n_fft/2 < T.  segan_stft_frames
+ * and segan_stft_overlap_add also require an even n_fft (SEGAN_EINVAL otherwise): for an odd one
+ * the padded index can pass the reach of one reflection and the frame count differs from
+ * torch.stft's. */
 int segan_stft_pitch(int n_fft);
 int segan_stft_basis(float* basis, int n_fft, int win, void* stream);
 int segan_stft_frames(const float* x, float* frames, int B, int T, int n_fft, int hop, int win,

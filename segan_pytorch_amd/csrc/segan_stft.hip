@@ -10,6 +10,11 @@
 // The product itself is segan_gemm (exact fp32 MFMA); this file holds the framing, the
 // power/log stage, their backward, and the overlap-add that returns the frame gradient to
 // the waveform.
+// The framing and the overlap-add take an EVEN n_fft only.  With n_fft/2 < T the largest padded
+// index is then at most T + n_fft/2 - 1 <= 2(T-1), which one reflection folds back into the row.
+// For an odd n_fft it can reach 2(T-1) + 1 (n_fft = win = 321, T = 161: index 321 of a row whose
+// mirror ends at 320), and the frame count 1 + T/hop is one more than torch.stft's when hop
+// divides T; no model option reaches one, so both entry points refuse it.
 #include "segan_common.h"
 #include <math.h>
 
@@ -64,6 +69,8 @@ extern "C" int segan_stft_frames(const float* x, float* frames, int B, int T, in
                                  int win, void* stream) {
   SEGAN_REQUIRE(x && frames, "stft_frames: NULL pointer");
   SEGAN_REQUIRE(B > 0 && T > 1 && hop > 0 && win >= 1 && win <= n_fft, "stft_frames: bad sizes");
+  SEGAN_REQUIRE(n_fft % 2 == 0, "stft_frames: odd n_fft=%d is not supported (n_fft must be even)",
+                n_fft);
   SEGAN_REQUIRE(n_fft / 2 < T, "stft_frames: reflect padding needs n_fft/2 < T");
   const int NF = 1 + T / hop;
   const int off = (n_fft - win) / 2 - n_fft / 2;
@@ -164,6 +171,8 @@ extern "C" int segan_stft_overlap_add(const float* dframes, float* dx, int B, in
                                       int hop, int win, void* stream) {
   SEGAN_REQUIRE(dframes && dx, "stft_overlap_add: NULL pointer");
   SEGAN_REQUIRE(B > 0 && T > 1 && hop > 0 && win >= 1 && win <= n_fft, "stft_overlap_add: bad sizes");
+  SEGAN_REQUIRE(n_fft % 2 == 0,
+                "stft_overlap_add: odd n_fft=%d is not supported (n_fft must be even)", n_fft);
   SEGAN_REQUIRE(n_fft / 2 < T, "stft_overlap_add: reflect padding needs n_fft/2 < T");
   const int NF = 1 + T / hop;
   const int off = (n_fft - win) / 2 - n_fft / 2;

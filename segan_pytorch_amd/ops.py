@@ -900,9 +900,17 @@ def stft_basis(n_fft, win, device):
     return _stft_basis_cache[key]
 
 
+def _stft_even(n_fft, what):
+    # one reflection reaches 2(T-1); an odd n_fft can ask for one sample more, and its frame
+    # count is not torch.stft's when hop divides T (segan_stft.hip refuses it as well)
+    if n_fft % 2:
+        raise ValueError('{}: odd n_fft={} is not supported (n_fft must be even)'.format(what, n_fft))
+
+
 def stft_frames(x, n_fft, hop, win):
-    """x [B, T] -> frames [B*NF, win] of the reflect-padded signal."""
+    """x [B, T] -> frames [B*NF, win] of the reflect-padded signal (even n_fft, n_fft/2 < T)."""
     _chk(x, 'x', 2)
+    _stft_even(n_fft, 'stft_frames')
     B, T = x.shape
     NF = 1 + T // hop
     fr = torch.empty((B * NF, win), device=x.device, dtype=torch.float32)
@@ -949,6 +957,7 @@ def powdb_bwd(S, ddb, nbins, eps=10e-20):
 
 def stft_overlap_add(dframes, B, T, n_fft, hop, win):
     _chk(dframes, 'dframes', 2)
+    _stft_even(n_fft, 'stft_overlap_add')
     dx = torch.empty((B, T), device=dframes.device, dtype=torch.float32)
     check(_lib.load().segan_stft_overlap_add(_ptr(dframes), _ptr(dx), B, T, n_fft, hop, win,
                                              _stream()), 'stft_overlap_add')

@@ -36,6 +36,40 @@ def test_host_deemphasis_matches_the_reference_loop(frows):
     assert np.abs(got - fx['x'].numpy()).max() < 5e-6
 
 
+# ---- the float64 restatements that tests/test_gpu_dense_sweep.py holds the kernels to -------------
+def test_ssnr_restatement_matches_the_reference(frows):
+    """ssnr_ref64 (float64, from the header comment of segan_audio.hip) against the reference's own
+    fp32 run: 1e-4, the bar test_device_ssnr_matches_the_reference holds the kernel to."""
+    from test_gpu_dense_sweep import ssnr_ref64
+    fx = frows['ssnr']
+    overall, mean, seg = ssnr_ref64(fx['clean'].numpy(), fx['deg'].numpy())
+    want = fx['segmental'].numpy()
+    assert seg.shape == want.shape and seg.dtype == np.float64
+    assert np.abs(seg - want).max() < 1e-4
+    assert np.abs(overall - fx['overall'].numpy()).max() < 1e-4
+    assert np.abs(mean - want.mean(1)).max() < 1e-4
+
+
+def test_pcm_restatement_matches_the_reference(frows):
+    """pcm_x64 / pcm_preemph64 against normalize_wave_minmax + pre_emphasize of the reference, bit
+    for bit in float64 (and so after the one cast to fp32)."""
+    from test_gpu_dense_sweep import pcm_prep_ref, pcm_preemph64, pcm_x64
+    fx = frows['pcm']
+    pcm = fx['pcm'].numpy()
+    x = pcm_x64(pcm)
+    assert x.dtype == np.float64 and np.array_equal(x, fx['normalized'].numpy())
+    want = fx['pre_emphasized'].numpy()
+    # the whole wav as one slice that starts it (element 0 of the row is ignored) ...
+    row = np.concatenate((x[:1], x))
+    assert np.array_equal(pcm_preemph64(row, fx['coef'], True), want)
+    # ... and a slice from its middle, through the [B, 2, T + 1] form the kernels take
+    beg, T = 8192, 4096
+    block = np.stack((pcm[beg - 1:beg + T], pcm[:T + 1]))[None]
+    clean, noisy = pcm_prep_ref(block, [0], fx['coef'])
+    assert clean.dtype == np.float32 and np.array_equal(clean[0], want[beg:beg + T].astype(np.float32))
+    assert np.array_equal(noisy[0], want[1:T + 1].astype(np.float32))
+
+
 # ---- f3: checkpoints written by the reference's Saver --------------------------------------------
 def test_checkpoint_written_by_the_reference_saver_loads(frows, tmp_path):
     from segan_pytorch_amd.models import SEGAN
