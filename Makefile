@@ -9,7 +9,7 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wal
 
 all: $(LIB)
 
-$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/segan_common.h $(CSRC)/segan_conv_shared.h $(CSRC)/segan_signal.h include/segan_hip.h
+$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/segan_common.h $(CSRC)/segan_conv_shared.h $(CSRC)/segan_conv_tile.h $(CSRC)/segan_signal.h include/segan_hip.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(LIB): $(OBJS)

@@ -19,29 +19,16 @@
 // discriminator's circular phase shift, both torch.cat's, the alpha skip scale,
 // BatchNorm-normalise and PReLU are all applied while the tile is staged
 // (segan_src), so none of those tensors is ever materialised in HBM.
-#include "segan_conv_shared.h"
+#include "segan_conv_tile.h"
 
-// Tile geometry: MB rows x NB columns per 256-thread workgroup, waves WM x (4/WM).
-//   F form: rows = output channels m; waves 2x2.
-//   T form: rows = (phase r, channel n) with ALL S phases of MB/S channels in one tile and
-//           waves 1x4 (NB=128) so that one lane ends up holding the S consecutive output
-//           samples S*q..S*q+S-1 of a channel: full-line stores instead of stride-S ones.
-//
-// What the instruction stream beside the MFMAs costs was measured (profiles/r02_mfma_issue_cost
+// Tile geometry, the tile epilogue and the stream-K fix-up: segan_conv_tile.h (shared with the
+// bf16 kernel).  What the instruction stream beside the MFMAs costs was measured (profiles/r02_mfma_issue_cost
 // .json): v_mfma_f32_32x32x2_f32 issues every 64 cycles per SIMD, and every VALU instruction
 // any wave of that SIMD issues takes ~5 of those cycles, every VMEM instruction ~25, a
 // ds_write_b32 ~4, a ds_write_b128 ~12; SALU and ds_read_b32 are (almost) free.  The staging
 // code of corr2_kernel is therefore built from buffer loads whose per-lane offsets never
 // change (wave-uniform parts go through the SGPR offset, masking through the descriptor's
 // range check), LDS-DMA for the weight tile, and per-wave-uniform transforms.
-template <int MB, int NB, int WM, int U>
-struct TileGeom {
-  static constexpr int S = 32 / U;
-  static constexpr int WN = 4 / WM;
-  static constexpr int NI = MB / (32 * WM);
-  static constexpr int NJ = NB / (32 * WN);
-  static constexpr int NPT = MB / S;   // T form: channels per tile
-};
 
 // which tile a workgroup works on, and which chunk range of it (stream-K pieces)
 struct TileWork {
@@ -90,343 +77,6 @@ struct TileIter {
     return false;
   }
 };
-
-// per-lane column bookkeeping of a tile: which (sample, time) the lane's NJ columns are and
-// where they sit in the LDS activation tile
-template <int NB, int WN, int NJ>
-__device__ __forceinline__ void lane_columns(const CorrArgs& a, const ColTile& ct, int wn, int l31,
-                                             int h, int (&col_b)[NJ], int (&col_t)[NJ],
-                                             int (&boff)[NJ]) {
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const int cl = wn * (NB / WN) + 32 * j + l31;
-    const int col = ct.col0 + cl;
-    if (col < a.Ctot) {
-      const int b = col / a.Tcols;
-      col_b[j] = b;
-      col_t[j] = col - b * a.Tcols;
-      boff[j] = cl + (b - ct.b0) * a.H + h;
-    } else {
-      col_b[j] = -1;
-      col_t[j] = 0;
-      boff[j] = h;
-    }
-  }
-}
-
-// accumulator slab of a stream-K piece: [NI*NJ*4][256] float4, thread-minor (coalesced 16-byte
-// accesses)
-template <int NI, int NJ>
-__device__ __forceinline__ void slab_store(float* slab, const f32x16 (&acc)[NI][NJ], int tid) {
-  f32x4* s4 = reinterpret_cast<f32x4*>(slab);
-#pragma unroll
-  for (int i = 0; i < NI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f32x4 v = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2],
-                         acc[i][j][4 * q + 3]};
-        s4[((i * NJ + j) * 4 + q) * 256 + tid] = v;
-      }
-}
-template <int NI, int NJ>
-__device__ __forceinline__ void slab_add(const float* slab, f32x16 (&acc)[NI][NJ], int tid) {
-  const f32x4* s4 = reinterpret_cast<const f32x4*>(slab);
-#pragma unroll
-  for (int i = 0; i < NI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f32x4 v = s4[((i * NJ + j) * 4 + q) * 256 + tid];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[i][j][4 * q + e] += v[e];
-      }
-}
-
-// ---- epilogue: bias, optional tanh, store of a finished tile ----
-template <int MB, int NB, int WM, int U, bool OUT_HI>
-__device__ __forceinline__ void corr_store_tile(
-    const CorrArgs& a, const f32x16 (&acc)[TileGeom<MB, NB, WM, U>::NI][TileGeom<MB, NB, WM, U>::NJ],
-    int m0, int n0, int wm, int h, const int (&col_b)[TileGeom<MB, NB, WM, U>::NJ],
-    const int (&col_t)[TileGeom<MB, NB, WM, U>::NJ]) {
-  using G = TileGeom<MB, NB, WM, U>;
-  constexpr int S = G::S, NI = G::NI, NJ = G::NJ, NPT = G::NPT;
-  if (!OUT_HI) {
-    // Interior tiles — all rows valid and in one destination, plain stores — take the fast form:
-    // buffer stores whose per-lane byte offsets are computed once per column (masked columns
-    // carry an out-of-range offset: the store is dropped), the row inside the tile goes through
-    // the scalar offset: no address arithmetic, row test or destination select per element (the
-    // generic form below spends ~30 VALU per stored value, a tenth of a 64-chunk tile's time).
-    {
-      float* fdst = m0 < a.OC0 ? a.out0 : a.out1;
-      const int foc = m0 < a.OC0 ? a.OC0 : a.OC1;
-      const int foch = m0 < a.OC0 ? m0 : m0 - a.OC0;
-      const long fbytes = (long)a.B * foc * a.Lout * 4;
-      if (a.act == SEGAN_ACT_NONE && m0 + MB <= a.Rvalid && (m0 + MB <= a.OC0 || m0 >= a.OC0) &&
-          fdst != nullptr && fbytes < 0x7fffffffL) {
-        const __amdgpu_buffer_rsrc_t ors =
-            __builtin_amdgcn_make_buffer_rsrc(fdst, 0, (int)fbytes, 0x00020000);
-        int ovo[NJ];
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-          ovo[j] = col_b[j] < 0 ? (int)0x80000000u
-                                : ((col_b[j] * foc + foch + 32 * wm * NI + 4 * h) * a.Lout + col_t[j]) * 4;
-        const int rowstep = a.Lout * 4;
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            const int rl = 32 * i + (e & 3) + 8 * (e >> 2);
-            float bs = 0.0f;
-            if (a.bias) bs = epi_bias(a.bias, m0 + 32 * wm * NI, rl, h);
-#pragma unroll
-            for (int j = 0; j < NJ; ++j)
-              __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, acc[i][j][e] + bs), ors,
-                                                    ovo[j], rl * rowstep, 0);
-          }
-        }
-        return;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int row = m0 + 32 * (wm * NI + i) + (e & 3) + 8 * (e >> 2) + 4 * h;
-        if (row >= a.Rvalid) continue;
-        // LO store: out[b, row, t]
-        float* dst;
-        int oc, och;
-        if (row < a.OC0) { dst = a.out0; oc = a.OC0; och = row; }
-        else { dst = a.out1; oc = a.OC1; och = row - a.OC0; }
-        if (dst == nullptr) continue;
-        const float bs = a.bias ? a.bias[row] : 0.0f;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          if (col_b[j] < 0) continue;
-          float v = acc[i][j][e] + bs;
-          if (a.act == SEGAN_ACT_TANH) v = tanhf(v);
-          dst[((size_t)col_b[j] * oc + och) * (size_t)a.Lout + col_t[j]] = v;
-        }
-      }
-    }
-  } else {
-    // HI store.  Row block ib of the tile is phase r = 32*ib / NPT of channels n0 + nl.
-    constexpr bool QUAD = (S == 4 && WM == 1 && NI == 4);  // lane holds all 4 phases of (n, q)
-    const int hl = a.o_padL + a.o_padR;
-    const long obytes = (long)a.B * a.Nout * a.Lout * 4;
-    const bool qfast = obytes < 0x7fffffffL;      // 32-bit byte offsets reach every output element
-    const __amdgpu_buffer_rsrc_t qrs = __builtin_amdgcn_make_buffer_rsrc(
-        a.out0, 0, (int)(qfast ? obytes : 0), 0x00020000);
-    if (QUAD && qfast && a.act == SEGAN_ACT_NONE && a.o_padL == 0 && a.o_roll == 0 &&
-        a.halo == nullptr && n0 + NPT <= a.Nout && a.Lout == 4 * a.Tcols) {
-      // deconv forward: a lane's four phase accumulators are four consecutive output samples
-      int ovo[NJ];
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-        ovo[j] = col_b[j] < 0 ? (int)0x80000000u
-                              : ((col_b[j] * a.Nout + n0 + 4 * h) * a.Lout + 4 * col_t[j]) * 4;
-      const int rowstep = a.Lout * 4;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int nl = (e & 3) + 8 * (e >> 2);
-        float bs = 0.0f;
-        if (a.bias) bs = epi_bias(a.bias, n0, nl, h);
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
-          const u32x4s o = {__builtin_bit_cast(unsigned, acc[0 % NI][j][e] + bs),
-                            __builtin_bit_cast(unsigned, acc[1 % NI][j][e] + bs),
-                            __builtin_bit_cast(unsigned, acc[2 % NI][j][e] + bs),
-                            __builtin_bit_cast(unsigned, acc[3 % NI][j][e] + bs)};
-          __builtin_amdgcn_raw_buffer_store_b128(o, qrs, ovo[j] + nl * rowstep, 0, 0);   // (*)
-        }
-      }
-      return;
-    }
-    int cb[NJ];          // columns still to be stored by the generic form below (-1: done / masked)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) cb[j] = col_b[j];
-    if (QUAD && qfast && a.act == SEGAN_ACT_NONE && n0 + NPT <= a.Nout) {
-      // conv data gradient (HI store with a left pad, a halo and possibly a roll): everything that
-      // depends on the COLUMN only — sample, the first of the lane's four output positions, the
-      // roll's wrap — is worked out once per column instead of once per stored vector; interior
-      // columns (all but the ~8 at a row's ends and the one on the wrap point) then store one
-      // 16-byte vector per channel row (the row offset added to the vector offset: (*) in segan_conv_shared.h).  The generic form below
-      // (~30 VALU per stored vector) costs a bf16 tile 40 % of its time and an fp32 tile 5-10 %.
-      int ovo[NJ];
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        ovo[j] = (int)0x80000000u;
-        if (col_b[j] >= 0) {
-          const int i0 = 4 * col_t[j] - a.o_padL;
-          int ib = i0 - a.o_roll;
-          if (ib < 0) ib += a.Lout;
-          if (ib >= a.Lout) ib -= a.Lout;
-          if (i0 >= 0 && i0 + 3 < a.Lout && ib + 3 < a.Lout) {
-            ovo[j] = ((col_b[j] * a.Nout + n0 + 4 * h) * a.Lout + ib) * 4;
-            cb[j] = -1;
-          }
-        }
-      }
-      const int rowstep = a.Lout * 4;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int nl = (e & 3) + 8 * (e >> 2);
-        float bs = 0.0f;
-        if (a.bias) bs = epi_bias(a.bias, n0, nl, h);
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
-          const u32x4s o = {__builtin_bit_cast(unsigned, acc[0 % NI][j][e] + bs),
-                            __builtin_bit_cast(unsigned, acc[1 % NI][j][e] + bs),
-                            __builtin_bit_cast(unsigned, acc[2 % NI][j][e] + bs),
-                            __builtin_bit_cast(unsigned, acc[3 % NI][j][e] + bs)};
-          __builtin_amdgcn_raw_buffer_store_b128(o, qrs, ovo[j] + nl * rowstep, 0, 0);   // (*)
-        }
-      }
-      bool left = false;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) left = left || cb[j] >= 0;
-      if (!left) return;
-    }
-    // Stride 2 (round 6): a lane holds BOTH phases of its channels — in row blocks ib and ib + NI/2
-    // (64 / 32 channels per tile), or in elements e and e + 8 of the one block of a 16-channel tile —
-    // i.e. two consecutive output samples: one 8-byte store per (channel, column) for the deconv
-    // forward and the interior columns of the conv data gradient, offsets once per column as in the
-    // stride-4 form above.  The stride-2 T form used to take the generic per-element path below
-    // (~30 VALU per stored value).
-    constexpr bool PAIR = (S == 2 && WM == 1 && (NI == 4 || NI == 2 || NI == 1));
-    if (PAIR && qfast && a.act == SEGAN_ACT_NONE && n0 + NPT <= a.Nout) {
-      int ovo[NJ];
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        ovo[j] = (int)0x80000000u;
-        if (col_b[j] >= 0) {
-          const int i0 = 2 * col_t[j] - a.o_padL;
-          int ib = i0 - a.o_roll;
-          if (ib < 0) ib += a.Lout;
-          if (ib >= a.Lout) ib -= a.Lout;
-          if (i0 >= 0 && i0 + 1 < a.Lout && ib + 1 < a.Lout) {
-            ovo[j] = ((col_b[j] * a.Nout + n0 + 4 * h) * a.Lout + ib) * 4;
-            cb[j] = -1;
-          }
-        }
-      }
-      const int rowstep = a.Lout * 4;
-      constexpr int NBLK = NI >= 2 ? NI / 2 : 1;      // 32-channel blocks of the tile
-      constexpr int NE = NI >= 2 ? 16 : 8;            // channel slots per block and lane
-#pragma unroll
-      for (int bk = 0; bk < NBLK; ++bk) {
-#pragma unroll
-        for (int e = 0; e < NE; ++e) {
-          const int nl = 32 * bk + (e & 3) + 8 * (e >> 2);
-          float bs = 0.0f;
-          if (a.bias) bs = epi_bias(a.bias, n0, nl, h);
-#pragma unroll
-          for (int j = 0; j < NJ; ++j) {
-            typedef unsigned u32x2s __attribute__((ext_vector_type(2)));
-            const float p0 = acc[bk][j][e];
-            const float p1 = NI >= 2 ? acc[(bk + NI / 2) % NI][j][e] : acc[0][j][(e + 8) % 16];
-            const u32x2s o = {__builtin_bit_cast(unsigned, p0 + bs), __builtin_bit_cast(unsigned, p1 + bs)};
-            __builtin_amdgcn_raw_buffer_store_b64(o, qrs, ovo[j] + nl * rowstep, 0, 0);   // (*)
-          }
-        }
-      }
-      bool left = false;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) left = left || cb[j] >= 0;
-      if (!left) return;
-    }
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        if (cb[j] < 0) continue;
-        const int q = col_t[j];
-        if (QUAD) {
-          const int n = n0 + (e & 3) + 8 * (e >> 2) + 4 * h;
-          if (n >= a.Nout) continue;
-          const float bs = a.bias ? a.bias[n] : 0.0f;
-          float v[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            v[r] = acc[r][j][e] + bs;
-            if (a.act == SEGAN_ACT_TANH) v[r] = tanhf(v[r]);
-          }
-          const size_t rowoff = (size_t)col_b[j] * a.Nout + n;
-          const int i0 = 4 * q - a.o_padL;
-          if (qfast && i0 >= 0 && i0 + 3 < a.Lout) {
-            // interior of the row (all but ~8 of its positions): the four phases are four
-            // consecutive samples, also after the roll unless they straddle its wrap point
-            int ib = i0 - a.o_roll;
-            if (ib < 0) ib += a.Lout;
-            if (ib >= a.Lout) ib -= a.Lout;
-            if (ib + 3 < a.Lout) {
-              typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
-              const u32x4s o = {__builtin_bit_cast(unsigned, v[0]), __builtin_bit_cast(unsigned, v[1]),
-                                __builtin_bit_cast(unsigned, v[2]), __builtin_bit_cast(unsigned, v[3])};
-              __builtin_amdgcn_raw_buffer_store_b128(o, qrs, (int)((rowoff * a.Lout + ib) * 4), 0, 0);
-              continue;
-            }
-          }
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int P = 4 * q + r;
-            int ii = P - a.o_padL;
-            if (ii >= 0 && ii < a.Lout) {
-              if (a.o_roll != 0) {
-                ii -= a.o_roll;
-                if (ii < 0) ii += a.Lout;
-                if (ii >= a.Lout) ii -= a.Lout;
-              }
-              a.out0[rowoff * (size_t)a.Lout + ii] = v[r];
-            } else if (a.halo != nullptr) {
-              if (ii < 0) a.halo[rowoff * hl + P] = v[r];
-              else if (ii - a.Lout < a.o_padR) a.halo[rowoff * hl + a.o_padL + (ii - a.Lout)] = v[r];
-            }
-          }
-        } else {
-#pragma unroll
-          for (int i = 0; i < NI; ++i) {
-            const int rloc = 32 * (wm * NI + i) + (e & 3) + 8 * (e >> 2) + 4 * h;
-            const int r = rloc / NPT;
-            const int n = n0 + rloc % NPT;
-            if (n >= a.Nout) continue;
-            float v = acc[i][j][e] + (a.bias ? a.bias[n] : 0.0f);
-            if (a.act == SEGAN_ACT_TANH) v = tanhf(v);
-            const int P = S * q + r;
-            int ii = P - a.o_padL;
-            const size_t rowoff = (size_t)col_b[j] * a.Nout + n;
-            if (ii >= 0 && ii < a.Lout) {
-              if (a.o_roll != 0) {
-                ii -= a.o_roll;
-                if (ii < 0) ii += a.Lout;
-                if (ii >= a.Lout) ii -= a.Lout;
-              }
-              a.out0[rowoff * (size_t)a.Lout + ii] = v;
-            } else if (a.halo != nullptr) {
-              if (ii < 0) a.halo[rowoff * hl + P] = v;
-              else if (ii - a.Lout < a.o_padR) a.halo[rowoff * hl + a.o_padL + (ii - a.Lout)] = v;
-            }
-          }
-        }
-      }
-    }
-  }
-}
-
-// F form: rows of a tile that all go to a NULL destination (the z half of the first decoder
-// layer's data gradient) are skipped
-template <int MB, bool OUT_HI>
-__device__ __forceinline__ bool tile_is_dead(const CorrArgs& a, int m0) {
-  if (OUT_HI) return false;
-  if (a.out0 == nullptr && m0 + MB <= a.OC0) return true;
-  if (a.out1 == nullptr && m0 >= a.OC0) return true;
-  return false;
-}
 
 // The MFMA loop over one staged chunk, shared by both kernels.  Operands of step s+2 are read
 // from LDS before the MFMAs of step s are issued (three named register sets; everything is
@@ -716,7 +366,7 @@ __global__ __launch_bounds__(256, 2) void corr_kernel(const CorrArgs a) {
   if (tw.partial)
     slab_store<NI, NJ>(a.sk_ws + (size_t)(blockIdx.x * 2 + tw.piece) * (MB * NB), acc, tid);
   else
-    corr_store_tile<MB, NB, WM, U, OUT_HI>(a, acc, m0, n0, wm, h, col_b, col_t);
+    corr_store_tile<MB, NB, WM, U, OUT_HI, true>(a, acc, m0, n0, wm, h, col_b, col_t);
   }  // tile loop
 }
 
@@ -1003,71 +653,8 @@ __global__ __launch_bounds__(256, (IN_HI && !BLK) ? 4 : 2) void corr2_kernel(con
   if (tw.partial)
     slab_store<NI, NJ>(a.sk_ws + (size_t)(blockIdx.x * 2 + tw.piece) * (MB * NB), acc, tid);
   else
-    corr_store_tile<MB, NB, WM, U, OUT_HI>(a, acc, m0, n0, wm, h, col_b, col_t);
+    corr_store_tile<MB, NB, WM, U, OUT_HI, true>(a, acc, m0, n0, wm, h, col_b, col_t);
   }  // tile loop
-}
-
-// Stream-K second pass: one workgroup per cut tile adds the slabs of its pieces in chunk
-// order and stores the tile.  Tiles that one workgroup happened to hold whole were stored by
-// the main kernel.
-template <int MB, int NB, int WM, int U, bool OUT_HI, int KC>
-__global__ __launch_bounds__(256) void corr_fixup_kernel(const CorrArgs a) {
-  using G = TileGeom<MB, NB, WM, U>;
-  constexpr int WN = G::WN, NI = G::NI, NJ = G::NJ, NPT = G::NPT;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // uniform: scalar bias loads (epi_bias)
-  const int wm = wave / WN, wn = wave % WN;
-  const int l31 = lane & 31, h = lane >> 5;
-  const int nch = (a.Ktot + KC - 1) / KC;
-  const int t = blockIdx.x;
-  const long u0 = (long)t * nch, u1 = u0 + nch - 1;
-  const int g_first = (int)(u0 / a.sk_units), g_last = (int)(u1 / a.sk_units);
-  if (g_first == g_last) return;
-  const int tile = a.sk_nfull + t;
-  const int rowtile = a.rt0 + tile / a.ncoltiles;
-  const int coltile = tile % a.ncoltiles;
-  const int m0 = rowtile * MB, n0 = rowtile * NPT;
-  if (tile_is_dead<MB, OUT_HI>(a, m0)) return;
-  const ColTile ct = make_coltile(coltile * NB, a.Tcols, NB);
-  int col_b[NJ], col_t[NJ], boff[NJ];
-  lane_columns<NB, WN, NJ>(a, ct, wn, l31, h, col_b, col_t, boff);
-  f32x16 acc[NI][NJ];
-#pragma unroll
-  for (int i = 0; i < NI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
-  // two pieces in flight at a time (the kernel is a pure stream: more loads outstanding per
-  // lane), always ADDED in chunk order
-  auto slab_of = [&](int g) {
-    const int piece = t - (int)(((long)g * a.sk_units) / nch);
-    return reinterpret_cast<const f32x4*>(a.sk_ws + (size_t)(g * 2 + piece) * (MB * NB));
-  };
-  constexpr int NV = NI * NJ * 4;
-  for (int g = g_first; g <= g_last; g += 2) {
-    const bool two = g + 1 <= g_last;
-    const f32x4* s0 = slab_of(g);
-    const f32x4* s1 = slab_of(two ? g + 1 : g);
-    f32x4 v0[NV], v1[NV];
-#pragma unroll
-    for (int q = 0; q < NV; ++q) v0[q] = s0[q * 256 + tid];
-    if (two) {
-#pragma unroll
-      for (int q = 0; q < NV; ++q) v1[q] = s1[q * 256 + tid];
-    }
-#pragma unroll
-    for (int q = 0; q < NV; ++q)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[q / (NJ * 4)][(q / 4) % NJ][4 * (q % 4) + e] += v0[q][e];
-    if (two) {
-#pragma unroll
-      for (int q = 0; q < NV; ++q)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[q / (NJ * 4)][(q / 4) % NJ][4 * (q % 4) + e] += v1[q][e];
-    }
-  }
-  corr_store_tile<MB, NB, WM, U, OUT_HI>(a, acc, m0, n0, wm, h, col_b, col_t);
 }
 
 // fold the reflect halo of a conv dgrad back into dx.  When L > padL + padR + 1 the padL left
@@ -1287,39 +874,6 @@ extern "C" void segan_debug_last_corr(int* out6) {
   for (int i = 0; i < 6; ++i) out6[i] = g_last_corr[i];
 }
 
-// ---- launch plumbing ---------------------------------------------------------------------
-// One process drives one GPU, but nothing here assumes it: what is cached is cached per device.
-static int cur_device() {
-  int d = 0;
-  (void)hipGetDevice(&d);
-  return d & 15;
-}
-
-template <typename K>
-static void allow_big_lds(K kern, bool (&done)[16]) {
-  const int d = cur_device();
-  if (!done[d]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    done[d] = true;
-  }
-}
-
-// workgroups resident per CU (registers / LDS), cached per device and LDS size
-template <typename K>
-static int resident_per_cu(K kern, size_t lds, int (&occ)[16], size_t (&occ_lds)[16]) {
-  const int d = cur_device();
-  if (occ[d] == 0 || occ_lds[d] != lds) {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(kern), 256,
-                                                     lds) != hipSuccess || nb < 1)
-      nb = 2;
-    occ[d] = nb > 4 ? 4 : nb;
-    occ_lds[d] = lds;
-  }
-  return occ[d];
-}
-
 // Data-parallel + stream-K plan of a launch of `ntiles` equal tiles of `nch` chunks.  All
 // workgroups do the same amount of work and several are resident per CU, so a one-tile-per-
 // workgroup launch takes ceil(tiles / resident) rounds; when the last round would leave more
@@ -1373,6 +927,8 @@ static int launch_corr_t(CorrArgs a, hipStream_t st, bool allow_sk) {
   // rows below rt0 all go to a NULL destination (the z half of the first decoder layer)
   a.rt0 = (!OUT_HI && a.out0 == nullptr) ? a.OC0 / MB : 0;
   const int ntiles = (nrowtiles - a.rt0) * a.ncoltiles;
+  a.tile_order = 0;                  // columns first: what TileIter hands out (read by the fix-up)
+  a.nrt = nrowtiles - a.rt0;
   const int nch = ceil_div(a.Ktot, KC);
   const unsigned grid = plan_streamk(a, ntiles, nch, resident_per_cu(kern, lds, occ, occ_lds),
                                      (size_t)MB * NB, allow_sk);
@@ -1380,8 +936,8 @@ static int launch_corr_t(CorrArgs a, hipStream_t st, bool allow_sk) {
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);
   if (int e = segan_check_launch("corr_kernel")) return e;
   if (a.sk_total > 0) {
-    hipLaunchKernelGGL((corr_fixup_kernel<MB, NB, WM, U, OUT_HI, KC>), dim3(ntiles - a.sk_nfull),
-                       dim3(256), 0, st, a);
+    hipLaunchKernelGGL((corr_fixup_kernel<MB, NB, WM, U, OUT_HI, true, 2>), dim3(ntiles - a.sk_nfull),
+                       dim3(256), 0, st, a, nch);
     return segan_check_launch("corr_fixup_kernel");
   }
   return SEGAN_OK;
@@ -1407,6 +963,8 @@ static int launch_corr2_x(CorrArgs a, hipStream_t st, bool allow_sk) {
   allow_big_lds(kern, attr_done);
   a.rt0 = (!OUT_HI && a.out0 == nullptr) ? a.OC0 / MB : 0;
   const int ntiles = (nrowtiles - a.rt0) * a.ncoltiles;
+  a.tile_order = 0;                  // columns first: what TileIter hands out (read by the fix-up)
+  a.nrt = nrowtiles - a.rt0;
   const int nch = ceil_div(a.Ktot, KC);
   const unsigned grid = plan_streamk(a, ntiles, nch, resident_per_cu(kern, lds, occ, occ_lds),
                                      (size_t)MB * NB, allow_sk, a.f_pair != 0);
@@ -1418,8 +976,8 @@ static int launch_corr2_x(CorrArgs a, hipStream_t st, bool allow_sk) {
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);
   if (int e = segan_check_launch("corr2_kernel")) return e;
   if (a.sk_total > 0) {
-    hipLaunchKernelGGL((corr_fixup_kernel<MB, NB, WM, U, OUT_HI, KC>), dim3(ntiles - a.sk_nfull),
-                       dim3(256), 0, st, a);
+    hipLaunchKernelGGL((corr_fixup_kernel<MB, NB, WM, U, OUT_HI, true, 2>), dim3(ntiles - a.sk_nfull),
+                       dim3(256), 0, st, a, nch);
     return segan_check_launch("corr_fixup_kernel");
   }
   return SEGAN_OK;

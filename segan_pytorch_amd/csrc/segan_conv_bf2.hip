@@ -22,19 +22,12 @@
 // TU * NI * NJ MFMAs — and nothing else.
 //
 // The packing pass is HBM-bound (4 B read, 2 B written per element and plane, coalesced both
-// ways).  Tile geometry, stream-K hybrid and epilogues are those of corr_bf_kernel.
-#include "segan_conv_shared.h"
+// ways).  Tile geometry, the tile epilogue (corr_store_tile, without the stride-2 pair stores) and
+// the stream-K fix-up kernel are the fp32 kernels' own: segan_conv_tile.h.
+#include "segan_conv_tile.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void split3b(float x, __bf16& p1, __bf16& p2, __bf16& p3) {
-  p1 = (__bf16)x;
-  const float r1 = x - (float)p1;
-  p2 = (__bf16)r1;
-  const float r2 = r1 - (float)p2;
-  p3 = (__bf16)r2;
-}
 
 // ====================================================================================
 // activation packing
@@ -124,262 +117,6 @@ __global__ __launch_bounds__(256) void act_pack_kernel(const PackArgs a) {
     *reinterpret_cast<u32x4*>(a.out + p * a.plane_elems + piece * 8) = __builtin_bit_cast(u32x4, pl[p]);
 }
 
-// ---- tile epilogue: bias, store (shared by the contraction kernel and the stream-K fix-up) ----
-template <int MB, int NB, int WM, int U, bool OUT_HI>
-__device__ __forceinline__ void bf2_store_tile(const CorrArgs& a,
-                                               const f32x16 (&acc)[MB / (32 * WM)][NB / (32 * (4 / WM))],
-                                               int m0, int n0, int wm, int h,
-                                               const int (&col_b)[NB / (32 * (4 / WM))],
-                                               const int (&col_t)[NB / (32 * (4 / WM))]) {
-  constexpr int S = 32 / U;
-  constexpr int WN = 4 / WM;
-  constexpr int NI = MB / (32 * WM);
-  constexpr int NJ = NB / (32 * WN);
-  constexpr int NPT = MB / S;
-  constexpr bool add_bias = true;
-  // ---- epilogue ----
-  // A bf16 tile spends 16x fewer matrix-pipe cycles per output element than an fp32 one, so the
-  // generic epilogue below (64-bit address arithmetic, row / destination tests and a bias load
-  // per element: ~30 VALU per stored value) cost as much as the tile's whole contraction.  Full
-  // interior tiles — all rows valid and in one destination, plain stores — take the fast form:
-  // buffer stores whose per-lane offsets are computed once per column (masked columns carry an
-  // out-of-range offset: the store is dropped), the row inside the tile goes through the scalar
-  // offset, no VALU per element.
-  if (!OUT_HI) {
-    float* fdst = m0 < a.OC0 ? a.out0 : a.out1;
-    const int foc = m0 < a.OC0 ? a.OC0 : a.OC1;
-    const int foch = m0 < a.OC0 ? m0 : m0 - a.OC0;
-    const long fbytes = (long)a.B * foc * a.Lout * 4;
-    const bool fast = a.act == SEGAN_ACT_NONE && m0 + MB <= a.Rvalid &&
-                      (m0 + MB <= a.OC0 || m0 >= a.OC0) && fdst != nullptr && fbytes < 0x7fffffffL;
-    if (fast) {
-      const __amdgpu_buffer_rsrc_t ors =
-          __builtin_amdgcn_make_buffer_rsrc(fdst, 0, (int)fbytes, 0x00020000);
-      int ovo[NJ];
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-        ovo[j] = col_b[j] < 0 ? (int)0x80000000u
-                              : ((col_b[j] * foc + foch + 32 * wm * NI + 4 * h) * a.Lout + col_t[j]) * 4;
-      const int rowstep = a.Lout * 4;
-#pragma unroll
-      for (int i = 0; i < NI; ++i) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int rl = 32 * i + (e & 3) + 8 * (e >> 2);
-          float bs = 0.0f;
-          if (a.bias && add_bias) bs = epi_bias(a.bias, m0 + 32 * wm * NI, rl, h);
-#pragma unroll
-          for (int j = 0; j < NJ; ++j)
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, acc[i][j][e] + bs), ors,
-                                                  ovo[j], rl * rowstep, 0);
-        }
-      }
-      return;
-    }
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int row = m0 + 32 * (wm * NI + i) + (e & 3) + 8 * (e >> 2) + 4 * h;
-        if (row >= a.Rvalid) continue;
-        float* dst;
-        int oc, och;
-        if (row < a.OC0) { dst = a.out0; oc = a.OC0; och = row; }
-        else { dst = a.out1; oc = a.OC1; och = row - a.OC0; }
-        if (dst == nullptr) continue;
-        const float bs = (a.bias && add_bias) ? a.bias[row] : 0.0f;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          if (col_b[j] < 0) continue;
-          float v = acc[i][j][e] + bs;
-          float* o = dst + ((size_t)col_b[j] * oc + och) * (size_t)a.Lout + col_t[j];
-          if (a.act == SEGAN_ACT_TANH) v = tanhf(v);
-          *o = v;
-        }
-      }
-    }
-  } else {
-    constexpr bool QUAD = (S == 4 && WM == 1 && NI == 4);
-    const long obytes = (long)a.B * a.Nout * a.Lout * 4;
-    if (QUAD && a.act == SEGAN_ACT_NONE && a.o_padL == 0 && a.o_roll == 0 &&
-        a.halo == nullptr && n0 + NPT <= a.Nout && a.Lout == 4 * a.Tcols && obytes < 0x7fffffffL) {
-      // deconv forward: a lane's four phase accumulators are four consecutive output samples
-      const __amdgpu_buffer_rsrc_t ors =
-          __builtin_amdgcn_make_buffer_rsrc(a.out0, 0, (int)obytes, 0x00020000);
-      int ovo[NJ];
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-        ovo[j] = col_b[j] < 0 ? (int)0x80000000u
-                              : ((col_b[j] * a.Nout + n0 + 4 * h) * a.Lout + 4 * col_t[j]) * 4;
-      const int rowstep = a.Lout * 4;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int nl = (e & 3) + 8 * (e >> 2);
-        float bs = 0.0f;
-        if (a.bias && add_bias) bs = epi_bias(a.bias, n0, nl, h);
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          const u32x4 o = {__builtin_bit_cast(unsigned, acc[0][j][e] + bs),
-                           __builtin_bit_cast(unsigned, acc[1][j][e] + bs),
-                           __builtin_bit_cast(unsigned, acc[2][j][e] + bs),
-                           __builtin_bit_cast(unsigned, acc[3][j][e] + bs)};
-          __builtin_amdgcn_raw_buffer_store_b128(o, ors, ovo[j] + nl * rowstep, 0, 0);   // (*)
-        }
-      }
-      return;
-    }
-    const bool qfast = obytes < 0x7fffffffL;     // 32-bit byte offsets reach every output element
-    const __amdgpu_buffer_rsrc_t qrs = __builtin_amdgcn_make_buffer_rsrc(
-        a.out0, 0, (int)(qfast ? obytes : 0), 0x00020000);
-    int cb[NJ];          // columns still to be stored by the generic form below (-1: done / masked)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) cb[j] = col_b[j];
-    if (QUAD && qfast && a.act == SEGAN_ACT_NONE && n0 + NPT <= a.Nout) {
-      // conv data gradient (HI store with a left pad, a halo and possibly a roll): what depends on
-      // the COLUMN only — sample, first of the lane's four output positions, the roll's wrap — is
-      // worked out once per column; interior columns store one 16-byte vector per channel row (row
-      // offset in the vector offset: (*) in segan_conv_shared.h), the few columns at a row's ends and on the wrap point go
-      // through the generic form below.  Measured with the stores compiled out (round 4): the
-      // generic form alone was 40 % of this kernel's time on enc1 / enc2's data gradients.
-      int ovo[NJ];
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        ovo[j] = (int)0x80000000u;
-        if (col_b[j] >= 0) {
-          const int i0 = 4 * col_t[j] - a.o_padL;
-          int ib = i0 - a.o_roll;
-          if (ib < 0) ib += a.Lout;
-          if (ib >= a.Lout) ib -= a.Lout;
-          if (i0 >= 0 && i0 + 3 < a.Lout && ib + 3 < a.Lout) {
-            ovo[j] = ((col_b[j] * a.Nout + n0 + 4 * h) * a.Lout + ib) * 4;
-            cb[j] = -1;
-          }
-        }
-      }
-      const int rowstep = a.Lout * 4;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int nl = (e & 3) + 8 * (e >> 2);
-        float bs = 0.0f;
-        if (a.bias && add_bias) bs = epi_bias(a.bias, n0, nl, h);
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          const u32x4 o = {__builtin_bit_cast(unsigned, acc[0 % NI][j][e] + bs),
-                           __builtin_bit_cast(unsigned, acc[1 % NI][j][e] + bs),
-                           __builtin_bit_cast(unsigned, acc[2 % NI][j][e] + bs),
-                           __builtin_bit_cast(unsigned, acc[3 % NI][j][e] + bs)};
-          __builtin_amdgcn_raw_buffer_store_b128(o, qrs, ovo[j] + nl * rowstep, 0, 0);   // (*)
-        }
-      }
-      bool left = false;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) left = left || cb[j] >= 0;
-      if (!left) return;
-    }
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        if (cb[j] < 0) continue;
-        const int q = col_t[j];
-        if (QUAD) {
-          const int n = n0 + (e & 3) + 8 * (e >> 2) + 4 * h;
-          if (n >= a.Nout) continue;
-          const float bs = (a.bias && add_bias) ? a.bias[n] : 0.0f;
-          float v[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            v[r] = acc[r][j][e] + bs;
-            if (a.act == SEGAN_ACT_TANH) v[r] = tanhf(v[r]);
-          }
-          const size_t rowoff = (size_t)col_b[j] * a.Nout + n;
-          const int i0 = 4 * q - a.o_padL;
-          if (i0 >= 0 && i0 + 3 < a.Lout) {
-            // interior of the row (all but ~8 of its positions): the four phases are four
-            // consecutive samples, also after the roll unless they straddle its wrap point
-            int ib = i0 - a.o_roll;
-            if (ib < 0) ib += a.Lout;
-            if (ib >= a.Lout) ib -= a.Lout;
-            if (ib + 3 < a.Lout) {
-              const u32x4 o = {__builtin_bit_cast(unsigned, v[0]), __builtin_bit_cast(unsigned, v[1]),
-                               __builtin_bit_cast(unsigned, v[2]), __builtin_bit_cast(unsigned, v[3])};
-              if (qfast)
-                __builtin_amdgcn_raw_buffer_store_b128(o, qrs, (int)((rowoff * a.Lout + ib) * 4), 0, 0);
-              else
-                *reinterpret_cast<u32x4*>(a.out0 + rowoff * (size_t)a.Lout + ib) = o;
-              continue;
-            }
-          }
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int P = 4 * q + r;
-            int ii = P - a.o_padL;
-            if (ii >= 0 && ii < a.Lout) {
-              if (a.o_roll != 0) {
-                ii -= a.o_roll;
-                if (ii < 0) ii += a.Lout;
-                if (ii >= a.Lout) ii -= a.Lout;
-              }
-              float* o = a.out0 + rowoff * (size_t)a.Lout + ii;
-              *o = v[r];
-            } else if (a.halo != nullptr) {
-              const int hl = a.o_padL + a.o_padR;
-              float* o = nullptr;
-              if (ii < 0) o = a.halo + rowoff * hl + P;
-              else if (ii - a.Lout < a.o_padR) o = a.halo + rowoff * hl + a.o_padL + (ii - a.Lout);
-              if (o) { *o = v[r]; }
-            }
-          }
-        } else {
-#pragma unroll
-          for (int i = 0; i < NI; ++i) {
-            const int rloc = 32 * (wm * NI + i) + (e & 3) + 8 * (e >> 2) + 4 * h;
-            const int r = rloc / NPT;
-            const int n = n0 + rloc % NPT;
-            if (n >= a.Nout) continue;
-            float v = acc[i][j][e] + ((a.bias && add_bias) ? a.bias[n] : 0.0f);
-            if (a.act == SEGAN_ACT_TANH) v = tanhf(v);
-            const int P = S * q + r;
-            int ii = P - a.o_padL;
-            const size_t rowoff = (size_t)col_b[j] * a.Nout + n;
-            if (ii >= 0 && ii < a.Lout) {
-              if (a.o_roll != 0) {
-                ii -= a.o_roll;
-                if (ii < 0) ii += a.Lout;
-                if (ii >= a.Lout) ii -= a.Lout;
-              }
-              float* o = a.out0 + rowoff * (size_t)a.Lout + ii;
-              *o = v;
-            } else if (a.halo != nullptr) {
-              const int hl = a.o_padL + a.o_padR;
-              float* o = nullptr;
-              if (ii < 0) o = a.halo + rowoff * hl + P;
-              else if (ii - a.Lout < a.o_padR) o = a.halo + rowoff * hl + a.o_padL + (ii - a.Lout);
-              if (o) { *o = v; }
-            }
-          }
-        }
-      }
-    }
-  }
-}
-
-// accumulator slab of a stream-K piece: [NI*NJ*4][256] float4, thread-minor
-template <int NI, int NJ>
-__device__ __forceinline__ void bf2_slab_store(float* slab, const f32x16 (&acc)[NI][NJ], int tid) {
-  f32x4* s4 = reinterpret_cast<f32x4*>(slab);
-#pragma unroll
-  for (int i = 0; i < NI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f32x4 v = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2],
-                         acc[i][j][4 * q + 3]};
-        s4[((i * NJ + j) * 4 + q) * 256 + tid] = v;
-      }
-}
-
 // ====================================================================================
 // contraction
 // ====================================================================================
@@ -419,11 +156,8 @@ __device__ __forceinline__ void bf2_wait_vm(int n) {
 
 template <int MB, int NB, int WM, int U, bool OUT_HI, int SHIFTMASK, int NPL, int TU>
 __global__ __launch_bounds__(256, (NPL == 1 && NB == 128) ? 3 : 2) void corr_bf2_kernel(const CorrArgs a, const Bf2Extra x) {
-  constexpr int S = 32 / U;
-  constexpr int WN = 4 / WM;
-  constexpr int NI = MB / (32 * WM);
-  constexpr int NJ = NB / (32 * WN);
-  constexpr int NPT = MB / S;
+  using G = TileGeom<MB, NB, WM, U>;
+  constexpr int WN = G::WN, NI = G::NI, NJ = G::NJ, NPT = G::NPT;
   constexpr int TCH = U / TU;          // weight stages per channel group
   constexpr int NSH = SHIFTMASK ? 2 : 1;
   constexpr int KI = 3;                // activation DMA instructions per wave, plane and group: RLs' <= 6 * 64
@@ -484,10 +218,7 @@ __global__ __launch_bounds__(256, (NPL == 1 && NB == 128) ? 3 : 2) void corr_bf2
   const int rowtile = a.rt0 + (a.tile_order ? tile - coltile * a.nrt : tile / a.ncoltiles);
   const int m0 = rowtile * MB;
   const int n0 = rowtile * NPT;
-  if (!OUT_HI) {
-    if (a.out0 == nullptr && m0 + MB <= a.OC0) continue;
-    if (a.out1 == nullptr && m0 >= a.OC0) continue;
-  }
+  if (tile_is_dead<MB, OUT_HI>(a, m0)) continue;
   const ColTile ct = make_coltile(coltile * NB, a.Tcols, NB);
 
   // ---- activation DMA: descriptor rebased to the tile's first sample, per-lane offsets of the
@@ -524,21 +255,7 @@ __global__ __launch_bounds__(256, (NPL == 1 && NB == 128) ? 3 : 2) void corr_bf2
 #pragma unroll
   for (int i = 0; i < NI; ++i) arow[i] = 32 * (wm * NI + i) + l31;
   int col_b[NJ], col_t[NJ];
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const int cl = wn * (NB / WN) + 32 * j + l31;
-    const int col = ct.col0 + cl;
-    if (col < a.Ctot) {
-      const int b = col / a.Tcols;
-      col_b[j] = b;
-      col_t[j] = col - b * a.Tcols;
-      boff[j] = cl + (b - ct.b0) * a.H;
-    } else {
-      col_b[j] = -1;
-      col_t[j] = 0;
-      boff[j] = 0;
-    }
-  }
+  lane_columns<NB, WN, NJ>(a, ct, wn, l31, 0, col_b, col_t, boff);   // the half h selects the LDS plane here
 
   f32x16 acc[NI][NJ];
 #pragma unroll
@@ -641,72 +358,10 @@ __global__ __launch_bounds__(256, (NPL == 1 && NB == 128) ? 3 : 2) void corr_bf2
   }
 
   if (partial)
-    bf2_slab_store<NI, NJ>(a.sk_ws + (size_t)(blockIdx.x * 2 + (tile - a.sk_nfull - first_sk_tile)) * (MB * NB), acc, tid);
+    slab_store<NI, NJ>(a.sk_ws + (size_t)(blockIdx.x * 2 + (tile - a.sk_nfull - first_sk_tile)) * (MB * NB), acc, tid);
   else
-    bf2_store_tile<MB, NB, WM, U, OUT_HI>(a, acc, m0, n0, wm, h, col_b, col_t);
+    corr_store_tile<MB, NB, WM, U, OUT_HI, false>(a, acc, m0, n0, wm, h, col_b, col_t);
   }  // tile loop
-}
-
-// Stream-K second pass (as corr_fixup_kernel of the fp32 path): one workgroup per cut tile adds
-// the slabs of its pieces in stage order — a fixed order, no atomics, no zero-filled outputs —
-// and stores the tile.
-template <int MB, int NB, int WM, int U, bool OUT_HI>
-__global__ __launch_bounds__(256) void bf2_fixup_kernel(const CorrArgs a, int nst) {
-  constexpr int S = 32 / U;
-  constexpr int WN = 4 / WM;
-  constexpr int NI = MB / (32 * WM);
-  constexpr int NJ = NB / (32 * WN);
-  constexpr int NPT = MB / S;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave / WN, wn = wave % WN;
-  const int l31 = lane & 31, h = lane >> 5;
-  const int t = blockIdx.x;
-  const long u0 = (long)t * nst, u1 = u0 + nst - 1;
-  const int g_first = (int)(u0 / a.sk_units), g_last = (int)(u1 / a.sk_units);
-  if (g_first == g_last) return;          // held whole by one workgroup: already stored
-  const int tile = a.sk_nfull + t;
-  const int coltile = a.tile_order ? tile / a.nrt : tile % a.ncoltiles;
-  const int rowtile = a.rt0 + (a.tile_order ? tile - coltile * a.nrt : tile / a.ncoltiles);
-  const int m0 = rowtile * MB, n0 = rowtile * NPT;
-  if (!OUT_HI) {
-    if (a.out0 == nullptr && m0 + MB <= a.OC0) return;
-    if (a.out1 == nullptr && m0 >= a.OC0) return;
-  }
-  const ColTile ct = make_coltile(coltile * NB, a.Tcols, NB);
-  int col_b[NJ], col_t[NJ];
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const int cl = wn * (NB / WN) + 32 * j + l31;
-    const int col = ct.col0 + cl;
-    if (col < a.Ctot) {
-      col_b[j] = col / a.Tcols;
-      col_t[j] = col - col_b[j] * a.Tcols;
-    } else {
-      col_b[j] = -1;
-      col_t[j] = 0;
-    }
-  }
-  f32x16 acc[NI][NJ];
-#pragma unroll
-  for (int i = 0; i < NI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
-  constexpr int NV = NI * NJ * 4;
-  for (int g = g_first; g <= g_last; ++g) {
-    const int piece = t - (int)(((long)g * a.sk_units) / nst);
-    const f32x4* s4 = reinterpret_cast<const f32x4*>(a.sk_ws + (size_t)(g * 2 + piece) * (MB * NB));
-    f32x4 v[NV];
-#pragma unroll
-    for (int q = 0; q < NV; ++q) v[q] = s4[q * 256 + tid];
-#pragma unroll
-    for (int q = 0; q < NV; ++q)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[q / (NJ * 4)][(q / 4) % NJ][4 * (q % 4) + e] += v[q][e];
-  }
-  bf2_store_tile<MB, NB, WM, U, OUT_HI>(a, acc, m0, n0, wm, h, col_b, col_t);
 }
 
 // ====================================================================================
@@ -896,14 +551,7 @@ static int launch_bf2(CorrArgs a, Bf2Extra x, hipStream_t st) {
   static bool attr_done[16];
   static int occ[16];
   static size_t occ_lds[16];
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  dev &= 15;
-  if (!attr_done[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_done[dev] = true;
-  }
+  allow_big_lds(kern, attr_done);
   const int nrowtiles = OUT_HI ? a.NP / (MB / S) : ceil_div(a.Rvalid, MB);
   a.rt0 = (!OUT_HI && a.out0 == nullptr) ? a.OC0 / MB : 0;
   const int ntiles = (nrowtiles - a.rt0) * a.ncoltiles;
@@ -932,15 +580,7 @@ static int launch_bf2(CorrArgs a, Bf2Extra x, hipStream_t st) {
     sk_on = e ? atoi(e) : 1;
   }
   if (sk_on && a.act == SEGAN_ACT_NONE && ntiles >= 64 && nst >= 8 && classic_eff < 0.97) {
-    if (occ[dev] == 0 || occ_lds[dev] != lds) {
-      int nb = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(kern), 256,
-                                                       lds) != hipSuccess || nb < 1)
-        nb = 1;
-      occ[dev] = nb > 4 ? 4 : nb;
-      occ_lds[dev] = lds;
-    }
-    const int G = segan_grid_slots(occ[dev]);
+    const int G = segan_grid_slots(resident_per_cu(kern, lds, occ, occ_lds, 1));
     const int rem = ntiles - (ntiles / G) * G;
     if (rem > 0 && a.sk_ws != nullptr && a.sk_ws_floats >= (size_t)G * 2 * MB * NB) {
       a.sk_nfull = ntiles - rem;
@@ -953,9 +593,9 @@ static int launch_bf2(CorrArgs a, Bf2Extra x, hipStream_t st) {
   segan_note_corr_launch(3, grid, a, ntiles);
   if (int e = segan_check_launch("corr_bf2_kernel")) return e;
   if (a.sk_total > 0) {
-    hipLaunchKernelGGL((bf2_fixup_kernel<MB, NB, WM, U, OUT_HI>), dim3(ntiles - a.sk_nfull), dim3(256),
-                       0, st, a, nst);
-    return segan_check_launch("bf2_fixup_kernel");
+    hipLaunchKernelGGL((corr_fixup_kernel<MB, NB, WM, U, OUT_HI, false, 1>), dim3(ntiles - a.sk_nfull),
+                       dim3(256), 0, st, a, nst);
+    return segan_check_launch("corr_fixup_kernel");
   }
   return SEGAN_OK;
 }
@@ -1012,8 +652,6 @@ static int bf2_prepare(CorrArgs& a, int U, int planes, void* scratch, size_t scr
   return SEGAN_OK;
 }
 
-static inline int bf_f_pitch2(int M) { return round_up(M, 128); }
-
 int segan_corr_bf2_f(CorrArgs& a, int U, const void* wp3, int planes, void* scratch,
                      size_t scratch_bytes, hipStream_t st) {
   if (a.Rvalid <= 64 || (U != 8 && U != 16)) {
@@ -1024,7 +662,7 @@ int segan_corr_bf2_f(CorrArgs& a, int U, const void* wp3, int planes, void* scra
   constexpr int NB = BF2_NB;
   if (int e = bf2_prepare<true>(a, U, planes, scratch, scratch_bytes, x, st, NB)) return e;
   x.wp3 = (const __bf16*)wp3;
-  a.RP = bf_f_pitch2(a.Rvalid);
+  a.RP = bf_f_pitch(a.Rvalid);
   x.w_plane = (long)x.ngroups * U * 2 * a.RP * 8;
   if (U == 8) return planes == 3 ? launch_bf2<128, 2, 8, true, false, 0, 3>(a, x, st)
                                  : launch_bf2<128, 2, 8, true, false, 0, 1>(a, x, st);

@@ -95,7 +95,6 @@ struct CorrArgs {
 // the NEXT row's value (tests/diag/diag_dgrad_epilogue.py).  One v_add per store instead.
 
 
-
 static inline int samples_per_tile(int Tcols, int NB) {
   if (Tcols >= NB) return (Tcols % NB == 0) ? 1 : 2;
   return (NB % Tcols == 0) ? NB / Tcols : (NB + Tcols - 2) / Tcols + 1;
@@ -142,6 +141,50 @@ __device__ __forceinline__ float epi_bias(const float* bias, int base, int rl0, 
   cfloat* bp = (cfloat*)bias + base;
   const float lo = bp[rl0], hi = bp[rl0 + 4];
   return h ? hi : lo;
+}
+
+// x = p1 + p2 + p3 to 24 bits: the three bf16 planes of the bf16x3 forms (plane 1 alone = bf16)
+__device__ __forceinline__ void split3b(float x, __bf16& p1, __bf16& p2, __bf16& p3) {
+  p1 = (__bf16)x;
+  const float r1 = x - (float)p1;
+  p2 = (__bf16)r1;
+  const float r2 = r1 - (float)p2;
+  p3 = (__bf16)r2;
+}
+
+// ---- launch plumbing ---------------------------------------------------------------------
+// One process drives one GPU, but nothing here assumes it: what is cached is cached per device.
+static inline int cur_device() {
+  int d = 0;
+  (void)hipGetDevice(&d);
+  return d & 15;
+}
+
+// kernels with more than 64 KiB of dynamic LDS: opt in once per kernel and device
+template <typename K>
+static void allow_big_lds(K kern, bool (&done)[16]) {
+  const int d = cur_device();
+  if (!done[d]) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    done[d] = true;
+  }
+}
+
+// workgroups resident per CU (registers / LDS), at most 4, cached per device and LDS size;
+// `fallback` when the query fails
+template <typename K>
+static int resident_per_cu(K kern, size_t lds, int (&occ)[16], size_t (&occ_lds)[16], int fallback = 2) {
+  const int d = cur_device();
+  if (occ[d] == 0 || occ_lds[d] != lds) {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(kern), 256,
+                                                     lds) != hipSuccess || nb < 1)
+      nb = fallback;
+    occ[d] = nb > 4 ? 4 : nb;
+    occ_lds[d] = lds;
+  }
+  return occ[d];
 }
 
 // packed-weight geometry (shared by the pack kernels and the launchers)

@@ -1,6 +1,6 @@
 // segan_wgrad.hip — the W contraction form (both weight gradients) on the exact-fp32 MFMA:
 //   dW[m,n,S*u+r] += sum_{b,t} lo[b,m,t] * HI_r[b,n,t+u]      (forms: see segan_conv.hip)
-#include "segan_conv_shared.h"
+#include "segan_conv_tile.h"
 
 // ====================================================================================
 // wgrad kernel
@@ -10,22 +10,6 @@
 template <int TK>
 __device__ __forceinline__ int wg_sdiv(int x, int Ls, int magic) {
   return (Ls >= TK) ? (x >= Ls ? 1 : 0) : ((x * magic) >> 16);
-}
-
-// partial tile of one contraction split: [NI*NJ*4][256] float4, thread-minor
-template <int NI, int NJ>
-__device__ __forceinline__ void wgrad_slab_store(float* slab, const f32x16 (&acc)[NI][NJ], int tid) {
-  f32x4* s4 = reinterpret_cast<f32x4*>(slab);
-#pragma unroll
-  for (int i = 0; i < NI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f32x4 v = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2],
-                         acc[i][j][4 * q + 3]};
-        s4[((i * NJ + j) * 4 + q) * 256 + tid] = v;
-      }
 }
 
 // deterministic mode: dw[m][n][k] += sum over the contraction splits, in split order
@@ -338,7 +322,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradArgs a) {
 
   // ---- epilogue: dw[m][n][S*u + r] += acc (atomics), or a slab for the ordered reduction ----
   if (a.w2_slabs) {
-    wgrad_slab_store<NI, NJ>(a.w2_slabs + ((size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x +
+    slab_store<NI, NJ>(a.w2_slabs + ((size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x +
                                            blockIdx.x) * (MB * NBT), acc, tid);
     return;
   }
@@ -602,7 +586,7 @@ __global__ __launch_bounds__(256, RB >= 4 ? 1 : 2) void wgrad_edge_kernel(const 
     }
   }
   if (a.w2_slabs) {
-    wgrad_slab_store<NIW, 1>(a.w2_slabs + (size_t)blockIdx.z * (MB * 64), out, tid);
+    slab_store<NIW, 1>(a.w2_slabs + (size_t)blockIdx.z * (MB * 64), out, tid);
     return;
   }
   const int cc = wn * 32 + l31;
@@ -873,7 +857,7 @@ __global__ __launch_bounds__(256, 2) void wgrad2_kernel(const WgradArgs a) {
 
   // ---- epilogue ----
   if (a.w2_slabs) {
-    wgrad_slab_store<NI, NJ>(a.w2_slabs + ((size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x +
+    slab_store<NI, NJ>(a.w2_slabs + ((size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x +
                                            blockIdx.x) * (MB * NBT), acc, tid);
     return;
   }
@@ -930,12 +914,6 @@ extern "C" void segan_debug_last_wgrad(int* out6) {
 }
 
 // ---- wgrad2 launch ----
-static int wg_cur_device() {
-  int d = 0;
-  (void)hipGetDevice(&d);
-  return d & 15;
-}
-
 // scratch layout of the fp32 weight gradient: [lo materialised: B*M*Ls floats, when lo has a
 // transform or two segments][slabs: blocks * 128*128 floats, deterministic mode]
 static size_t wgrad2_slab_floats(int tiles, int nsplit, int MB = 128) { return (size_t)tiles * nsplit * MB * 128; }
@@ -991,22 +969,10 @@ static int launch_wgrad2(WgradArgs& a, hipStream_t st, bool deterministic, float
   static bool attr_done[16];
   static int occ_c[16];
   static size_t occ_lds[16];
-  const int d = wg_cur_device();
-  if (!attr_done[d]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_done[d] = true;
-  }
-  if (occ_c[d] == 0 || occ_lds[d] != lds) {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(kern), 256,
-                                                     lds) != hipSuccess || nb < 1)
-      nb = 2;
-    occ_c[d] = nb > 4 ? 4 : nb;
-    occ_lds[d] = lds;
-  }
+  allow_big_lds(kern, attr_done);
+  const int occ = resident_per_cu(kern, lds, occ_c, occ_lds);
   int tiles, nsplit, cps, nch;
-  wgrad2_plan(a, U, occ_c[d], tiles, nsplit, cps, nch, MB);
+  wgrad2_plan(a, U, occ, tiles, nsplit, cps, nch, MB);
   a.w2_cps = cps;
   a.w2_nch = nch;
   a.w2_slabs = nullptr;
@@ -1022,7 +988,7 @@ static int launch_wgrad2(WgradArgs& a, hipStream_t st, bool deterministic, float
   }
   const int ncol = ceil_div(a.Cv, 128 / U), nrow = ceil_div(a.M, MB);
   g_last_wgrad[0] = 2; g_last_wgrad[1] = tiles; g_last_wgrad[2] = nsplit; g_last_wgrad[3] = cps;
-  g_last_wgrad[4] = occ_c[d]; g_last_wgrad[5] = a.w2_nld;
+  g_last_wgrad[4] = occ; g_last_wgrad[5] = a.w2_nld;
   hipLaunchKernelGGL(kern, dim3(ncol, nrow, nsplit), dim3(256), lds, st, a);
   if (int e = segan_check_launch("wgrad2_kernel")) return e;
   if (deterministic) {
@@ -1083,12 +1049,7 @@ static int launch_wgrad_tile(WgradArgs& a, hipStream_t st, float* slabs, size_t 
   const size_t lds = (size_t)(2 * MB * (TK + 4) + 2 * CVW * a.RLw) * sizeof(float);
   auto kern = wgrad_kernel<U, TK, LO_ID, HI_ID, MB, NBT>;
   static bool attr_done[16];
-  const int d = wg_cur_device();
-  if (!attr_done[d]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_done[d] = true;
-  }
+  allow_big_lds(kern, attr_done);
   a.w2_slabs = nullptr;
   if (nsplit == 1) slabs = nullptr;      // unsplit: every dw element is touched exactly once
   if (slabs) {
@@ -1165,12 +1126,7 @@ static int launch_wgrad_edge_tile(WgradArgs& a, hipStream_t st, float* slabs, si
   const size_t lds = lds_red > lds_win ? lds_red : lds_win;
   auto kern = wgrad_edge_kernel<U, RB, NN, LO_ID, HI_ID>;
   static bool attr_done[16];
-  const int d = wg_cur_device();
-  if (!attr_done[d]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_done[d] = true;
-  }
+  allow_big_lds(kern, attr_done);
   hipLaunchKernelGGL(kern, dim3(1, 1, nwg), dim3(256), lds, st, a, spw);
   if (int e = segan_check_launch("wgrad_edge_kernel")) return e;
   if (slabs) {

@@ -21,14 +21,6 @@
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ void wsplit3b(float x, __bf16& p1, __bf16& p2, __bf16& p3) {
-  p1 = (__bf16)x;
-  const float r1 = x - (float)p1;
-  p2 = (__bf16)r1;
-  const float r2 = r1 - (float)p2;
-  p3 = (__bf16)r2;
-}
-
 // ---- lo: fp32 lo[b][m][t] (with its transform) -> planes [p][sg][t][Mp][8 samples] ----------
 // 64 time steps x 16 rows through LDS: a thread reads 4 consecutive time steps of its row for the
 // 8 samples as float4 (16 lanes = one 256-byte run per row and sample), the block writes 16 rows
@@ -76,7 +68,7 @@ __global__ __launch_bounds__(256) void wgrad_pack_lo2_kernel(const segan_src lo,
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         __bf16 p1, p2, p3;
-        wsplit3b(v[e][i], p1, p2, p3);
+        split3b(v[e][i], p1, p2, p3);
         pl[0][e] = p1; pl[1][e] = p2; pl[2][e] = p3;
       }
 #pragma unroll
@@ -157,7 +149,7 @@ __global__ __launch_bounds__(256) void wgrad_pack_hi_kernel(const segan_src hi, 
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       __bf16 p1, p2, p3;
-      wsplit3b(v[e][r], p1, p2, p3);
+      split3b(v[e][r], p1, p2, p3);
       pl[0][e] = p1; pl[1][e] = p2; pl[2][e] = p3;
     }
     const int cv = n * S + r;
@@ -419,14 +411,7 @@ static int launch_wbf2(WgradArgs& w, void* scratch, size_t scratch_bytes, hipStr
   nsplit = ceil_div(a.nchunks, a.cps);
   const size_t lds = (size_t)(2 * NPL * TQ * 128 + 2 * NPL * BINS * 64) * 16;
   static bool attr_done[16];
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  dev &= 15;
-  if (!attr_done[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_bf2_kernel<U, NPL, TQ>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_done[dev] = true;
-  }
+  allow_big_lds(&wgrad_bf2_kernel<U, NPL, TQ>, attr_done);
   hipLaunchKernelGGL((wgrad_bf2_kernel<U, NPL, TQ>), dim3(ncol, nrow, nsplit), dim3(256), lds, st, a);
   segan_note_wgrad_launch(3, ncol * nrow, nsplit, a.cps);
   return segan_check_launch("wgrad_bf2_kernel");

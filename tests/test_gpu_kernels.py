@@ -1136,6 +1136,118 @@ def test_deconv_layers_at_batch_scale_bf16(prec, name, M0, M1, N, Ls, B):
         assert dx0 is None
 
 
+# One tile epilogue serves the fp32 and the bf16 kernels.  Its fast stores (buffer stores per row,
+# 16-byte quad stores at stride 4, 8-byte pair stores at stride 2 in fp32) are taken only by tiles
+# whose rows are all real channels; one channel fewer and the same tile takes the generic
+# per-element form.  Each case is run with C and with C - 1 channels (the last slice of the same
+# weight and bias dropped): same kernel, same tile plan, and the common channels are the same bits.
+EPILOGUE_CASES = [
+    # op, sizes (B = 2, K = 31); `drop` names the dimension that loses its last channel
+    ('deconv_fwd', dict(M=32, N=32, Ls=128, S=4)),                   # quad
+    ('deconv_fwd', dict(M=32, N=64, Ls=128, S=2)),                   # pair (fp32), 128-row tile
+    ('deconv_fwd', dict(M=32, N=32, Ls=128, S=2)),                   # pair (fp32), 64-row tile
+    ('deconv_fwd', dict(M=32, N=16, Ls=128, S=2)),                   # pair (fp32), 32-row tile
+    ('conv_dgrad', dict(M=40, N=32, L=1024, S=4, roll=-3)),          # quad with halo and roll
+    ('conv_dgrad', dict(M=40, N=64, L=1024, S=4, roll=2)),
+    ('conv_fwd', dict(M=128, N=16, L=512, S=4)),                     # F form interior buffer stores
+    ('deconv_dgrad', dict(M=128, N=16, Ls=128, S=4, M0=64)),         # two destinations
+]
+_epilogue_refs = {}
+
+
+def _epilogue_inputs(op, g):
+    """fp32 inputs of a case and its fp64 outputs (computed once, shared by the precisions)."""
+    key = (op, tuple(sorted(g.items())))
+    if key not in _epilogue_refs:
+        B, K, S, M, N = 2, 31, g['S'], g['M'], g['N']
+        if op == 'deconv_fwd':
+            x, w, b = rnd(B, M, g['Ls'], seed=31), rnd(M, N, K, seed=32, scale=0.1), rnd(N, seed=33)
+            ref = [deconv_ref(x.double(), w.double(), b.double(), S)]
+        elif op == 'conv_dgrad':
+            x, w, b = rnd(B, M, g['L'] // S, seed=31), rnd(M, N, K, seed=32, scale=0.1), None
+            x0 = torch.zeros(B, N, g['L'], dtype=torch.float64, requires_grad=True)
+            conv_ref(x0, w.double(), None, S, g['roll']).backward(x.double())
+            ref = [x0.grad]
+        elif op == 'conv_fwd':
+            x, w, b = rnd(B, N, g['L'], seed=31), rnd(M, N, K, seed=32, scale=0.1), rnd(M, seed=33)
+            ref = [conv_ref(x.double(), w.double(), b.double(), S)]
+        else:
+            x, w, b = rnd(B, N, S * g['Ls'], seed=31), rnd(M, N, K, seed=32, scale=0.1), None
+            x0 = torch.zeros(B, M, g['Ls'], dtype=torch.float64, requires_grad=True)
+            deconv_ref(x0, w.double(), None, S).backward(x.double())
+            ref = [x0.grad[:, :g['M0']], x0.grad[:, g['M0']:]]
+        _epilogue_refs[key] = (x, w, b, ref)
+    return _epilogue_refs[key]
+
+
+def _epilogue_run(ops, op, g, x, w, b, drop):
+    """The op with the last `drop` (0 / 1) channels of its output dimension left out."""
+    xg = x.to(DEV)
+    if op == 'deconv_fwd':
+        n = g['N'] - drop
+        out = [ops.deconv1d_fwd(ops.Src(xg), w[:, :n].contiguous().to(DEV), b[:n].to(DEV), g['S'])]
+    elif op == 'conv_dgrad':
+        n = g['N'] - drop
+        out = [ops.conv1d_dgrad(xg, w[:, :n].contiguous().to(DEV), g['L'], g['S'], roll=g['roll'])]
+    elif op == 'conv_fwd':
+        m = g['M'] - drop
+        out = [ops.conv1d_fwd(ops.Src(xg), w[:m].to(DEV), b[:m].to(DEV), g['S'])]
+    else:
+        m = g['M'] - drop
+        out = list(ops.deconv1d_dgrad(xg, w[:m].to(DEV), g['S'], g['M0']))
+    return out, ops.last_corr_launch()
+
+
+@pytest.mark.parametrize('prec', ['fp32', 'bf16x3', 'bf16'])
+def test_fast_and_generic_epilogues_store_the_same_bits(prec):
+    ops = _ops()
+    tol = TOL if prec == 'fp32' else PREC_TOL[prec]
+    for op, g in EPILOGUE_CASES:
+        x, w, b, ref = _epilogue_inputs(op, g)
+        ops.set_precision(prec)
+        try:
+            full, info_full = _epilogue_run(ops, op, g, x, w, b, 0)
+            less, info_less = _epilogue_run(ops, op, g, x, w, b, 1)
+        finally:
+            ops.set_precision('fp32')
+        what = (op, g)
+        # 3 = corr_bf2_kernel: an entry point that declines silently runs the fp32 form instead
+        assert info_full['kernel'] == (2 if prec == 'fp32' else 3), what
+        assert (info_full['kernel'], info_full['tiles']) == (info_less['kernel'], info_less['tiles']), what
+        for f, r in zip(full, ref):
+            assert f.shape == r.shape and max_rel(f, r) < tol, what
+        # the last tensor is the one that lost a channel; the others are whole
+        for f, s in zip(full[:-1], less[:-1]):
+            assert torch.equal(f, s), what
+        c = less[-1].shape[1]
+        assert c == full[-1].shape[1] - 1 and torch.equal(full[-1][:, :c], less[-1]), what
+
+
+def test_stream_k_fixup_is_order_fixed_bf16():
+    """bf16 enc3 at B = 80: the cut tiles of the stream-K tail are summed by the fix-up kernel the
+    fp32 kernels use, slabs in chunk order — forward and data gradient are the same bits twice."""
+    ops = _ops()
+    name, N, M, L, roll, B = next(c for c in SCALE_CONV if c[0] == 'enc3' and c[5] == 80)
+    S, K = 4, 31
+    xg, slg = rnd(B, N, L, seed=11).to(DEV), (rnd(N, seed=12).abs() * 0.3).to(DEV)
+    wg, bg = rnd(M, N, K, seed=13, scale=0.05).to(DEV), rnd(M, seed=14).to(DEV)
+    dag = rnd(B, M, L // S, seed=15).to(DEV)
+    src = ops.Src(xg, slope=slg)
+    ops.set_precision('bf16')
+    try:
+        out = ops.conv1d_fwd(src, wg, bg, S, roll=roll)
+        info_f = ops.last_corr_launch()
+        out2 = ops.conv1d_fwd(src, wg, bg, S, roll=roll)
+        dx = ops.conv1d_dgrad(dag, wg, L, S, roll=roll)
+        info_t = ops.last_corr_launch()
+        dx2 = ops.conv1d_dgrad(dag, wg, L, S, roll=roll)
+    finally:
+        ops.set_precision('fp32')
+    assert info_f['kernel'] == 3 and info_t['kernel'] == 3, (info_f, info_t)
+    assert info_f['streamk'] or info_t['streamk'], (info_f, info_t)
+    assert torch.equal(out, out2) and torch.equal(dx, dx2)
+
+
 def l2_rel(a, b):
     a, b = a.detach().double().cpu(), b.detach().double().cpu()
     return ((a - b).norm() / b.norm().clamp_min(1e-300)).item()
