@@ -44,7 +44,15 @@ extern "C" {
  * (each vector may be NULL = identity; c indexes the concatenated channel axis).
  * This is how PReLU (modules.py:101), BatchNorm-normalise (modules.py:100), the
  * skip scale alpha and both torch.cat's (generator.py:76,205) are folded into the
- * consumer's load instead of being materialised. */
+ * consumer's load instead of being materialised.
+ * Alignment of p0 / p1 (each segment is contiguous [B, Ci, L]): 4 bytes wherever the source is an
+ * activation that is staged sample by sample — the input of segan_conv1d_fwd and
+ * segan_deconv1d_fwd and the `hi` operand of segan_wgrad, in every precision (scalar and
+ * one-dword buffer loads in the fp32 kernels; the bf16 packing passes read S consecutive samples
+ * through vector types declared 4-byte aligned).  16 bytes for the `lo` operand of segan_wgrad,
+ * which every kernel reads four samples at a time (float4 loads, 16-byte LDS-DMA; Ls % 4 == 0
+ * keeps the rows aligned): segan_wgrad returns -1 with a message for a lo pointer that is not.
+ * scale / shift / slope are read element by element: 4 bytes. */
 typedef struct segan_src {
   const float* p0;
   const float* p1; /* NULL when C1 == 0 */

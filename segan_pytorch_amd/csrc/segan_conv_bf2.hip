@@ -630,6 +630,7 @@ static int bf2_prepare(CorrArgs& a, int U, int planes, void* scratch, size_t scr
   }
   PackArgs pa;
   pa.identity = (!a.in.scale && !a.in.shift && !a.in.slope) ? 1 : 0;
+  a.xf_mode = a.in.shift ? 2 : (pa.identity ? 0 : 1);      // for the launch record only
   if (int e = segan_src_defaults(&a.in, st, "corr_bf2")) return e;
   pa.in = a.in;
   pa.out = (__bf16*)scratch;

@@ -924,6 +924,19 @@ static bool wgrad2_geometry_ok(const WgradArgs& a, int U) {
   return a.Ls >= 8 && (WG2_TK % a.Ls) == 0;
 }
 
+// wgrad2_kernel stages the MIDDLE chunks of a sample (neither its first nor its last: Ls >= 3 TK)
+// from one linear offset, stored index = padded coordinate - padL - roll, without the reflect fold,
+// the zero mask or the roll's wrap.  That holds when the padded coordinates those chunks touch,
+// S TK .. S (Ls - TK + U - 2) + S - 1, map into [0, Lhi) both before and after the roll; any other
+// padL / roll takes the general kernel.
+static bool wgrad2_middle_ok(const WgradArgs& a, int U) {
+  if (a.Ls < 3 * WG2_TK) return true;
+  const int S = 32 / U;
+  const long first = (long)S * WG2_TK - a.padL;
+  const long last = (long)S * (a.Ls - WG2_TK + U - 2) + S - 1 - a.padL;
+  return first >= 0 && last < a.Lhi && first - a.roll >= 0 && last - a.roll < a.Lhi;
+}
+
 static void wgrad2_plan(const WgradArgs& a, int U, int occ, int& tiles, int& nsplit, int& cps,
                         int& nch, int MB = 128) {
   const int ncol = ceil_div(a.Cv, 128 / U), nrow = ceil_div(a.M, MB);
@@ -1187,6 +1200,12 @@ static int launch_wgrad_fp32(WgradArgs& a, hipStream_t st, bool deterministic, f
   const size_t lo_floats = (size_t)a.B * a.M * a.Ls;
   const bool lo_plain = !a.lo.scale && !a.lo.shift && !a.lo.slope && a.lo.C1 == 0;
   bool fast = wgrad2_geometry_ok(a, U);
+  // wgrad2_kernel reads a padded zero as an out-of-range buffer load and transforms it like a
+  // stored sample: with a shift it would become prelu(shift[c]).  As corr2_ok does for the
+  // forward, zero padding with a shifted hi takes the general kernel, which masks after the
+  // transform (reflect padding has no implicit zeros inside the K taps)
+  if (a.mode == SEGAN_PAD_ZERO && a.hi.shift) fast = false;
+  if (fast && !wgrad2_middle_ok(a, U)) fast = false;
   if (fast && !lo_plain && (scratch == nullptr || scratch_floats < lo_floats)) fast = false;
   size_t used = (fast && !lo_plain) ? lo_floats : 0;
   if (deterministic) {
@@ -1252,6 +1271,9 @@ extern "C" int segan_wgrad(const segan_src* lo, const segan_src* hi, float* dw, 
   SEGAN_REQUIRE(mode == SEGAN_PAD_REFLECT || mode == SEGAN_PAD_ZERO, "wgrad: bad pad mode");
   if (int e = check_src(lo, M, "wgrad(lo)")) return e;
   if (int e = check_src(hi, N, "wgrad(hi)")) return e;
+  // every kernel reads lo as 16-byte vectors (float4 loads, 16-byte LDS-DMA): see segan_src
+  SEGAN_REQUIRE((((uintptr_t)lo->p0 | (lo->C1 > 0 ? (uintptr_t)lo->p1 : 0)) & 15) == 0,
+                "wgrad(lo): segment pointers must be 16-byte aligned");
   const int L = S * Ls;
   SEGAN_REQUIRE(roll > -L && roll < L, "wgrad: |roll| must be < L");
   WgradArgs a = {};
