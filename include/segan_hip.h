@@ -732,6 +732,63 @@ int segan_fir_rows(const float* x, const int* lengths, const float* prev, const 
                    const int* K, int nf, int kmax, const int* ids, int rows, int T, void* y,
                    int y_dtype, void* prev_out, int* status, void* stream);
 
+/* ---- on-the-fly whispered speech: noise-excited LPC resynthesis -------
+ * fp32 rows x [rows][T] at 16 kHz, row r restricted to its first lengths[r] samples (device
+ * int[rows], clamped to 0 .. T; NULL: all T), prev float[rows] (NULL: zeros) the sample before the
+ * row; rows <= 65535, T <= 2^30.  Index j = n + 1 (j = 0 is prev); frame f = 0 .. F-1, F = len /
+ * SEGAN_WHISPER_H + 2, covers j in [(f-1) H, (f+1) H); Fmax = segan_whisper_frames(T) is the frame
+ * stride of every per-frame array.  All arithmetic is fp64 with every operation rounded on its
+ * own, in an order fixed by sample and frame index: no atomics, no scratch, a row's result is
+ * bitwise independent of the other rows and of T beyond len.
+ *   segan_whisper_noise: u[r][i] = the unit-variance noise sample j0 + i of seeds[r] (device
+ *     long long[rows]): the four words of Philox4x32-10 at counter (lo32(J), hi32(J), 0, 0), J =
+ *     j + 2^20, key (lo32(seed), hi32(seed)), summed as integers, less 2 (2^32 - 1), divided by
+ *     sqrt((2^64 - 1) / 3).  -2^20 <= j0 <= 2^31.
+ *   segan_whisper_lags: r [rows][Fmax][P + 1]: the lags 0 .. P of window[m] * xe over each frame
+ *     (window double[N], lagwin double[P + 1], both on the device), times lagwin[l], r[0] times
+ *     1.0001.  Frames from F on come out zero.
+ *   segan_whisper_lpc: n sets of lags r [n][P + 1] -> a [n][P + 1] (a[0] = 1), sigma [n] = sqrt(E
+ *     / 192), order int[n]: Levinson-Durbin, stopped at order m - 1 with the higher coefficients
+ *     zero when k_m is not |k_m| < 1 or E has fallen to 2^-40 r[0].  r[0] <= 0 or NaN (a silent
+ *     frame): a = [1, 0 ..], sigma = 0, order = 0.
+ *   segan_whisper_synth: per frame, from zero state and after SEGAN_WHISPER_WU warm-up samples,
+ *     v[j] = e[j] - a[P] v[j-P] - .. - a[1] v[j-1] with e[j] = (sigma (u[j] - tau u[j-1])) /
+ *     sqrt(1 + tau tau), tau = tilts[r] (device double[rows]); window[m] v goes to ws (at least
+ *     rows * N * Fmax doubles); y[j] = the earlier frame's share + the later one's, divided by
+ *     peak[r] = max |y[0 .. len]| when that exceeds 1.  y[r][n] = y[n + 1], zero from len on, and
+ *     prev_out[r] = y[0], of y_dtype (SEGAN_DT_F32, rounded once, or SEGAN_DT_F64).  status
+ *     int[rows]: SEGAN_WHISPER_ST_SILENT = every frame of the row is silent,
+ *     SEGAN_WHISPER_ST_TILT = tau outside [0, 1): the row and prev are copied, peak = 0.  nsilent
+ *     int[rows] = silent frames below F; minorder int[rows] = the lowest order among the others
+ *     (P without any).
+ *   segan_whisper_rows: the three in turn on `stream`; ws holds segan_whisper_ws_doubles(rows, T).
+ * Added without a change of SEGAN_ABI_VERSION: the exports are purely additive. */
+#define SEGAN_WHISPER_N 512
+#define SEGAN_WHISPER_H 256
+#define SEGAN_WHISPER_P 16
+#define SEGAN_WHISPER_WU 256
+#define SEGAN_WHISPER_ST_SILENT 1
+#define SEGAN_WHISPER_ST_TILT 2
+int segan_whisper_frames(int T);
+long long segan_whisper_ws_doubles(int rows, int T);
+int segan_whisper_noise(const long long* seeds, long long j0, int count, int rows, double* u,
+                        void* stream);
+int segan_whisper_lags(const float* x, const int* lengths, const float* prev, const double* window,
+                       const double* lagwin, int rows, int T, double* r, void* stream);
+int segan_whisper_lpc(const double* r, long long n, double* a, double* sigma, int* order,
+                      void* stream);
+int segan_whisper_synth(const float* x, const int* lengths, const float* prev, const double* r,
+                        const double* a, const double* sigma, const int* order,
+                        const long long* seeds, const double* tilts, const double* window, int rows,
+                        int T, double* ws, long long ws_doubles, void* y, int y_dtype,
+                        void* prev_out, double* peak, int* status, int* nsilent, int* minorder,
+                        void* stream);
+int segan_whisper_rows(const float* x, const int* lengths, const float* prev,
+                       const long long* seeds, const double* tilts, const double* window,
+                       const double* lagwin, int rows, int T, double* ws, long long ws_doubles,
+                       void* y, int y_dtype, void* prev_out, double* peak, int* status,
+                       int* nsilent, int* minorder, void* stream);
+
 /* ---- optimizers (model.py:219-228) ---------------------------------------------------- */
 /* torch.optim.RMSprop (no momentum, not centered): sq = alpha*sq + (1-alpha)*g*g;
  * p -= lr * g / (sqrt(sq) + eps), over a flat arena of n floats. */

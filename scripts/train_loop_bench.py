@@ -13,7 +13,8 @@ row is mixed on the loader's side stream.  `--reverb` (op
 `--reverb_rirs` over four synthetic 4000-tap impulse responses: every item's clean wave is
 reverberated on the side stream first.  `--distort` (opt-in) adds `--distort
 clip chop bandlimit` at the default settings: every item is clipped, chopped or band limited on the
-side stream.
+side stream.  `--whisper` (opt-in) adds `--whisper` at the default settings:
+every item is resynthesised as pseudo-whisper on the side stream first.
 """
 import argparse
 import json
@@ -39,6 +40,8 @@ ap.add_argument('--reverb', action='store_true',
 ap.add_argument('--reverb_taps', type=int, default=4000)
 ap.add_argument('--distort', action='store_true',
                 help='clip, chop or band limit every item on the fly (train.py --distort)')
+ap.add_argument('--whisper', action='store_true',
+                help='whisper every item on the fly (train.py --whisper)')
 args = ap.parse_args()
 
 os.makedirs(args.tmp, exist_ok=True)
@@ -74,6 +77,8 @@ if args.reverb:
     extra = extra + ['--reverb_rirs', rdir, '--reverb_max_taps', str(args.reverb_taps)]
 if args.distort:
     extra = extra + ['--distort', 'clip', 'chop', 'bandlimit']
+if args.whisper:
+    extra = extra + ['--whisper']
 
 import train
 from segan_pytorch_amd.models import core
@@ -112,7 +117,7 @@ ms = 1e3 * (t1 - state['t0']) / timed
 out = {'what': 'train.py --pcm_shard (default SEGAN+ net, batch {}, RMSprop, host z, int16 shard '
                'through worker gathers + GPU prep): {} epochs of {} batches, the first epoch is '
                'warm-up, device-synchronised clock around the rest'.format(args.batch, args.epochs, per_epoch),
-       'additive': bool(args.additive), 'reverb': bool(args.reverb), 'distort': bool(args.distort), 'ms_per_batch': ms, 'chunks_per_s': args.batch * 1e3 / ms, 'batches_timed': timed}
+       'additive': bool(args.additive), 'reverb': bool(args.reverb), 'distort': bool(args.distort), 'whisper': bool(args.whisper), 'ms_per_batch': ms, 'chunks_per_s': args.batch * 1e3 / ms, 'batches_timed': timed}
 try:
     import glob
     b = json.load(open(sorted(glob.glob(os.path.join(ROOT, 'profiles', 'r[0-9][0-9]_bench_line.json')))[-1]))

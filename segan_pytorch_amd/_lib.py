@@ -132,7 +132,14 @@ SIGNATURES = {
     'segan_chop_rows': (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     'segan_fir_rows': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, c_int, c_int, _P, c_int, _P, _P,
                                _P]),
-    'segan_rmsprop_step': (c_int, [_P, _P, _P, c_float, c_float, c_float, c_int64, _P]),
+    'segan_whisper_frames': (c_int, [c_int]),
+    'segan_whisper_ws_doubles': (c_int64, [c_int, c_int]),
+    'segan_whisper_noise': (c_int, [_P, c_int64, c_int, c_int, _P, _P]),
+    'segan_whisper_lags': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, _P]),
+    'segan_whisper_lpc': (c_int, [_P, c_int64, _P, _P, _P, _P]),
+    'segan_whisper_synth': (c_int, [_P] * 10 + [c_int, c_int, _P, c_int64, _P, c_int] + [_P] * 6),
+    'segan_whisper_rows': (c_int, [_P] * 7 + [c_int, c_int, _P, c_int64, _P, c_int] + [_P] * 6),
+    'segan_rmsprop_step':(c_int, [_P, _P, _P, c_float, c_float, c_float, c_int64, _P]),
     'segan_adam_step': (c_int, [_P, _P, _P, _P, c_float, c_double, c_double, c_float, c_int, c_int64,
                                 _P]),
     'segan_fill': (c_int, [_P, c_float, c_int64, _P]),

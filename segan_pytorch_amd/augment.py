@@ -4,7 +4,9 @@ HIP kernels (`ops.asl_p56`, `ops.additive_mix`), batched.  And on-the-fly reverb
 14): `Reverb` convolves each row with a room impulse response of an `RIRBank`
 (`ops.reverb_rows`).  And three signal-level distortions (section 17): `Clip` (amplitude clipping,
 `ops.clip_rows`), `Chop` (chunks of speech removed, `ops.chop_rows`), `BandLimit` (a zero-phase
-low-pass, `ops.fir_rows`), and `Distort`, which applies one of them per row."""
+low-pass, `ops.fir_rows`), and `Distort`, which applies one of them per row.  And whispered speech
+(section 18): `Whisper` replaces the voiced excitation by noise under the same spectral envelope
+(`ops.whisper_rows`)."""
 import glob
 import os
 
@@ -524,7 +526,8 @@ class Distort(object):
       3. chop's draws for its rows likewise (`Chop.draw`);
       4. bandlimit's draws for its rows likewise (`BandLimit.draw`).
     Each op then runs on its own rows and the results are scattered back.  The generators of the
-    member objects are not used."""
+    member objects are not used.  In `PCMShardLoader` this is the third of four stages: whisper,
+    reverb, distort, additive (`datasets._STAGES`); `Whisper` is a stage of its own, not a kind."""
 
     def __init__(self, kinds, seed=None):
         items = list(kinds.items()) if isinstance(kinds, dict) else [
@@ -590,6 +593,54 @@ class Distort(object):
     def __call__(self, wav):
         """Distort one waveform (numpy array or tensor, any shape: flattened)."""
         return _one_wave(self.apply, wav)
+
+
+# ---------------------------------------------------------------------------------
+# whispered speech (DESIGN.md section 18).  Every default below is this project's own choice, not
+# taken from a paper.
+# ---------------------------------------------------------------------------------
+class Whisper(_RowDistortion):
+    """Pseudo-whisper by noise-excited LPC resynthesis (`ops.whisper_rows`): every frame keeps its
+    spectral envelope and energy, the glottal excitation is replaced by noise.  Per row a noise
+    seed and a spectral tilt tau drawn uniformly from `tilts` (each in [0, 1); 0 = white
+    excitation, 0.9 lifts the excitation by nearly 6 dB per octave).  `lag_hz`: the width of the
+    lag window that smooths the envelope.  Not a `Distort` kind: whisper is a property of the
+    talker and runs before the room."""
+
+    def __init__(self, tilts=(0.0, 0.5, 0.9), lag_hz=120.0, seed=None):
+        self.tilts = np.asarray(list(tilts), dtype=np.float64).reshape(-1)
+        if len(self.tilts) == 0 or not ((self.tilts >= 0) & (self.tilts < 1)).all():
+            raise ValueError('Whisper: tilts must be non-empty and lie in [0, 1), got {}'.format(
+                list(tilts)))
+        ops.whisper_tables(lag_hz)      # refuses a lag_hz it cannot use
+        self.lag_hz = float(lag_hz)
+        self.rng = np.random.default_rng(seed)
+
+    def draw(self, rng, rows, seeds=None, tilt_ids=None):
+        """(seeds int64 [rows], tilt_ids int64 [rows]) from two vectorised draws in this order:
+        the rows' noise seeds, uniform over 0 .. 2^63 - 1, then their tilt ids.  Values passed in
+        are checked, kept and not drawn."""
+        if seeds is None:
+            seeds = rng.integers(0, 2 ** 63, size=rows, dtype=np.int64)
+        else:
+            seeds = np.asarray(seeds, dtype=np.int64).reshape(-1)
+            if len(seeds) != rows or (seeds < 0).any():
+                raise ValueError('Whisper: {} seeds in 0 .. 2^63 - 1 expected, got {}'.format(
+                    rows, seeds.tolist()))
+        return seeds, _draw_ids(rng, len(self.tilts), rows, tilt_ids, 'Whisper', 'tilt ids')
+
+    def apply(self, wave, generator=None, seeds=None, tilt_ids=None, lengths=None, prev=None):
+        """wave [B, T] (fp32 CUDA) -> (whispered [B, T], info).  `seeds`, `tilt_ids` (per row)
+        replace the draws.  info: the dict of `ops.whisper_rows` (prev = the whispered sample
+        preceding each row, status, nsilent, minorder, peak) plus seeds, tilt_ids, tilts (numpy,
+        host)."""
+        ops._chk(wave, 'wave', 2)
+        seeds, ids = self.draw(self.rng if generator is None else generator, wave.shape[0], seeds,
+                               tilt_ids)
+        out, info = ops.whisper_rows(wave, seeds, self.tilts[ids], lengths, prev,
+                                     lag_hz=self.lag_hz)
+        info.update(seeds=seeds, tilt_ids=ids, tilts=self.tilts[ids])
+        return out, info
 
 
 class ComposeAdditive(object):

@@ -211,31 +211,7 @@ __global__ __launch_bounds__(QW_THREADS) void wss_kernel(
 // 659-716) in every lane, R and [1, -a] rounded to fp32 as lpcoeff returns them, both quadratic
 // forms A toeplitz(R_clean) A^T in fp64 from those, log of the ratio.  R_clean[0] == 0 yields NaN.
 // ---------------------------------------------------------------------------------
-template <int P, bool ROUND32 = true>   // ROUND32: [1, -a] rounded to fp32 as lpcoeff returns it
-__device__ __forceinline__ void levinson_lpc(const double (&R)[P + 1], double (&A)[P + 1]) {
-  double a[P];
-#pragma unroll
-  for (int j = 0; j < P; ++j) a[j] = 1.0;
-  double E = R[0];
-#pragma unroll
-  for (int i = 0; i < P; ++i) {
-    double sum = 0.0;
-#pragma unroll
-    for (int j = 0; j < i; ++j) sum += a[j] * R[i - j];
-    const double rc = (R[i + 1] - sum) / E;
-    double na[P];
-#pragma unroll
-    for (int j = 0; j < i; ++j) na[j] = a[j] - rc * a[i - 1 - j];
-#pragma unroll
-    for (int j = 0; j < i; ++j) a[j] = na[j];
-    a[i] = rc;
-    E = (1 - rc * rc) * E;
-  }
-  A[0] = 1.0;
-#pragma unroll
-  for (int j = 0; j < P; ++j) A[j + 1] = ROUND32 ? (double)(float)(-a[j]) : -a[j];
-}
-
+// levinson_lpc: segan_signal.h (shared with the whisper stage)
 template <int P>
 __device__ __forceinline__ double quad_toeplitz(const double (&A)[P + 1], const double (&R)[P + 1]) {
   double q = 0.0;

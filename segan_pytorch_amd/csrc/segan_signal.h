@@ -37,6 +37,54 @@ __device__ __forceinline__ int segan_row_samples(const int* __restrict__ lengths
   return L < 0 ? 0 : (L > T ? T : L);
 }
 
+// Levinson-Durbin in fp64 (lpcoeff, utils.py:659-716), every lane on its own: A = [1, -a] of the
+// order-P predictor of the lags R.  ROUND32: A rounded to fp32 as lpcoeff returns it (LLR).
+// GUARD (the whisper stage): the recursion stops at order m - 1, with the higher coefficients
+// zero, when the reflection coefficient k_m is not |k_m| < 1 or when the error E has fallen to
+// efloor R[0]; *Eout and *order are then what that order left.  Without GUARD the operations and
+// their order are what LLR and CD have always run; Eout and order are not touched.
+template <int P, bool ROUND32 = true, bool GUARD = false>
+__device__ __forceinline__ void levinson_lpc(const double (&R)[P + 1], double (&A)[P + 1],
+                                             double efloor = 0.0, double* Eout = nullptr,
+                                             int* order = nullptr) {
+  double a[P];
+#pragma unroll
+  for (int j = 0; j < P; ++j) a[j] = 1.0;
+  double E = R[0];
+  const double floorE = efloor * R[0];
+  bool go = true;
+  int ord = 0;
+#pragma unroll
+  for (int i = 0; i < P; ++i) {
+    if (GUARD) go = go && E > floorE;
+    double sum = 0.0;
+#pragma unroll
+    for (int j = 0; j < i; ++j) sum += a[j] * R[i - j];
+    const double rc = (R[i + 1] - sum) / E;
+    if (GUARD) go = go && fabs(rc) < 1.0;
+    if (!GUARD || go) {
+      double na[P];
+#pragma unroll
+      for (int j = 0; j < i; ++j) na[j] = a[j] - rc * a[i - 1 - j];
+#pragma unroll
+      for (int j = 0; j < i; ++j) a[j] = na[j];
+      a[i] = rc;
+      E = (1 - rc * rc) * E;
+      ord = i + 1;
+    }
+  }
+  A[0] = 1.0;
+#pragma unroll
+  for (int j = 0; j < P; ++j) {
+    const double c = (GUARD && j >= ord) ? 0.0 : -a[j];
+    A[j + 1] = ROUND32 ? (double)(float)c : c;
+  }
+  if (GUARD) {
+    *Eout = E;
+    *order = ord;
+  }
+}
+
 // ceil(L p / q): the samples L samples become when resampled by p / q
 __host__ __device__ inline long long segan_resampled_len(long long L, int p, int q) {
   return (L * p + q - 1) / q;

@@ -283,6 +283,10 @@ class _BatchIndexDataset(Dataset):
 # waves, whether the sample preceding a slice that starts its wav is zeroed before the transform
 # sees it, and the key of the transform's output in the stage's records.
 _STAGES = (
+    # augment.Whisper: the wave resynthesised from its LPC envelope with a
+    # noise excitation.  A property of the talker, so it comes before the room, the channel and
+    # the noise; the preceding sample is a sample of the same signal and takes part in the frames
+    ('whisper', 'apply', True, 'out'),
     # augment.Reverb: the wave convolved with a drawn RIR, as if silence
     # preceded the slice; the preceding sample takes part, so it is zero at the start of a wav
     ('reverb', 'apply', True, 'wet'),
@@ -311,14 +315,16 @@ class PCMShardLoader(object):
                  num_workers=2, additive=None, additive_prob=1.0, additive_seed=None,
                  record_additive=False, reverb=None, reverb_prob=1.0, reverb_seed=None,
                  record_reverb=False, distort=None, distort_prob=1.0, distort_seed=None,
-                 record_distort=False):
+                 record_distort=False, whisper=None, whisper_prob=1.0, whisper_seed=None,
+                 record_whisper=False):
         from torch.utils.data import RandomSampler
         # per stage of _STAGES: self.<stage>, <stage>_prob, <stage>_rng (its own stream of draws)
         # and <stage>_records
         for stage, obj, prob, seed, record in (
                 ('additive', additive, additive_prob, additive_seed, record_additive),
                 ('reverb', reverb, reverb_prob, reverb_seed, record_reverb),
-                ('distort', distort, distort_prob, distort_seed, record_distort)):
+                ('distort', distort, distort_prob, distort_seed, record_distort),
+                ('whisper', whisper, whisper_prob, whisper_seed, record_whisper)):
             if obj is not None and not 0.0 <= float(prob) <= 1.0:
                 raise ValueError('{}_prob must lie in 0 .. 1, got {}'.format(stage, prob))
             setattr(self, stage, obj)
@@ -378,7 +384,8 @@ class PCMShardLoader(object):
         sample preceding the slice beside it (`ops.pcm16_wave`) - or, for an item that an earlier
         stage replaced (`done`: items ascending, waves [n, T], prevs [n]), that stage's wave and
         preceding sample.  So levels, scale factors, thresholds and filters are taken on the wave
-        as the stages before left it: noise is mixed into the reverberant or distorted wave.  Where
+        as the stages before left it: the whispered wave is reverberated, noise is mixed into the
+        reverberant or distorted wave.  Where
         the table says so, the preceding sample is zero where the slice starts its wav (nothing
         precedes a wav).
 

@@ -2037,6 +2037,184 @@ def fir_rows(x, bank, K, ids, lengths=None, prev=None, out_dtype=None):
     return y, dict(prev=prev_out, status=status)
 
 
+# ---------------------------------------------------------------------------------
+# whispered speech: noise-excited LPC resynthesis
+# ---------------------------------------------------------------------------------
+WHISPER_N = 512          # SEGAN_WHISPER_N: frame
+WHISPER_H = 256          # SEGAN_WHISPER_H: hop
+WHISPER_P = 16           # SEGAN_WHISPER_P: order
+WHISPER_WU = 256         # SEGAN_WHISPER_WU: warm-up samples of the synthesis filter
+WHISPER_SRATE = 16000
+WHISPER_SILENT = 1       # status bits of whisper_rows (SEGAN_WHISPER_ST_*)
+WHISPER_TILT = 2
+_whisper_tables_cache = {}
+_whisper_ws = {}
+
+
+def whisper_tables(lag_hz=120.0):
+    """(window float64 [512], lagwin float64 [17]) on the host: the periodic Hann window w[m] = 0.5
+    - 0.5 cos(2 pi m / 512) and the lag window g[l] = exp(-(2 pi lag_hz l / 16000)^2 / 2).
+    Restated by scripts/whisper_oracle.py (hann, lag_window): keep them alike."""
+    lag_hz = float(lag_hz)
+    if not 0.0 <= lag_hz <= 1000.0:       # also refuses NaN
+        raise ValueError('whisper: lag_hz must lie in 0 .. 1000 Hz, got {}'.format(lag_hz))
+    m = np.arange(WHISPER_N, dtype=np.float64)
+    lag = np.arange(WHISPER_P + 1, dtype=np.float64)
+    return (0.5 - 0.5 * np.cos(2.0 * np.pi * m / WHISPER_N),
+            np.exp(-0.5 * (2.0 * np.pi * lag_hz * lag / WHISPER_SRATE) ** 2))
+
+
+def _whisper_tables(device, lag_hz):
+    """`whisper_tables` on `device`, uploaded once per device and lag_hz."""
+    key = (device, float(lag_hz))
+    if key not in _whisper_tables_cache:
+        w, g = whisper_tables(lag_hz)
+        pair = (torch.from_numpy(w).to(device), torch.from_numpy(g).to(device))
+        torch.cuda.current_stream(device).synchronize()      # other streams use them next
+        _whisper_tables_cache[key] = pair
+    return _whisper_tables_cache[key]
+
+
+def whisper_frames(T):
+    return int(T) // WHISPER_H + 2
+
+
+def _whisper_workspace(doubles, device):
+    """The workspace of `whisper_rows` (86 MB at [300, 16384]), kept per (device, stream) and grown
+    on demand like `_reverb_workspace`."""
+    key = (device, _stream().value)
+    ws = _whisper_ws.get(key)
+    if ws is None or ws.numel() < doubles:
+        ws = _whisper_ws[key] = torch.empty(doubles, device=device, dtype=torch.float64)
+    return ws
+
+
+def _whisper_seeds(what, seeds, rows, device):
+    def ok(t):
+        if t.numel() and int(t.min()) < 0:
+            raise ValueError('{}: seeds must lie in 0 .. 2^63 - 1, got {}'.format(what, t.tolist()))
+
+    return _row_arg(what, 'seeds', seeds, (rows,), torch.int64, device, ok)
+
+
+def _whisper_args(what, x, seeds, tilts, lengths, prev):
+    rows, T, lens = _distort_rows(what, x, lengths, prev)
+
+    def tilt_ok(t):
+        f = t.to(torch.float64)
+        if not bool(((f >= 0) & (f < 1)).all()):
+            raise ValueError('{}: tilts must lie in [0, 1), got {}'.format(what, f.tolist()))
+
+    s_d = _whisper_seeds(what, seeds, rows, x.device)
+    t_d = _row_arg(what, 'tilts', tilts, (rows,), torch.float64, x.device, tilt_ok)
+    return rows, T, lens, s_d, t_d
+
+
+def _whisper_out_dtype(what, out_dtype):
+    out_dtype = torch.float32 if out_dtype is None else out_dtype
+    if out_dtype not in (torch.float32, torch.float64):
+        raise TypeError('{}: out_dtype must be torch.float32 or torch.float64, got {}'.format(
+            what, out_dtype))
+    return out_dtype
+
+
+def whisper_noise(seeds, j0, count, device=None):
+    """u float64 [rows, count]: the samples j0 .. j0 + count - 1 of the excitation of each seed
+    (host integers in 0 .. 2^63 - 1, or a CUDA int64 tensor): zero mean, unit variance, Philox4x32-10
+    (DESIGN.md section 18).  -2^20 <= j0 <= 2^31."""
+    if isinstance(seeds, torch.Tensor) and seeds.is_cuda:
+        device = seeds.device
+    elif device is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    rows = int(seeds.numel()) if isinstance(seeds, torch.Tensor) else int(np.asarray(seeds).size)
+    if rows == 0 or rows > DISTORT_MAX_ROWS:
+        raise ValueError('whisper_noise: 1 .. {} seeds, got {}'.format(DISTORT_MAX_ROWS, rows))
+    count = _int_arg(count, 'whisper_noise: count', 1, (1 << 31) - 1)
+    j0 = _int_arg(j0, 'whisper_noise: j0', -(1 << 20), 1 << 31)
+    s_d = _whisper_seeds('whisper_noise', seeds, rows, torch.device(device))
+    u = torch.empty((rows, count), device=s_d.device, dtype=torch.float64)
+    check(_lib.load().segan_whisper_noise(_ptr(s_d), j0, count, rows, _ptr(u), _stream()),
+          'whisper_noise')
+    return u
+
+
+def whisper_lpc(r):
+    """Levinson-Durbin with the whisper stage's guards on lags r (fp64 CUDA [..., 17]): dict(a [...,
+    17], sigma [...], order int32 [...]).  The recursion stops at order m - 1, the higher
+    coefficients zero, when k_m is not |k_m| < 1 or E has fallen to 2^-40 r[0]; r[0] <= 0: a = [1,
+    0 ..], sigma = 0, order = 0."""
+    _chk(r, 'r', None, torch.float64)
+    if r.dim() < 1 or r.shape[-1] != WHISPER_P + 1 or r.numel() == 0:
+        raise TypeError('whisper_lpc: r must be float64 [..., {}]'.format(WHISPER_P + 1))
+    n = r.numel() // (WHISPER_P + 1)
+    a = torch.empty_like(r)
+    sigma = torch.empty(r.shape[:-1], device=r.device, dtype=torch.float64)
+    order = torch.empty(r.shape[:-1], device=r.device, dtype=torch.int32)
+    check(_lib.load().segan_whisper_lpc(_ptr(r), n, _ptr(a), _ptr(sigma), _ptr(order), _stream()),
+          'whisper_lpc')
+    return dict(a=a, sigma=sigma, order=order)
+
+
+def whisper_stages(x, seeds, tilts, lengths=None, prev=None, lag_hz=120.0):
+    """`whisper_rows` stage by stage through the library's separate entry points (tests, timing):
+    dict(r, a [rows, F, 17], sigma, order [rows, F] with F = T // 256 + 2 (a row's own frames are
+    the first len // 256 + 2), y64 [rows, T], prev64 [rows], peak, status, nsilent, minorder)."""
+    rows, T, lens, s_d, t_d = _whisper_args('whisper_stages', x, seeds, tilts, lengths, prev)
+    w, g = _whisper_tables(x.device, lag_hz)
+    lib = _lib.load()
+    dev, F = x.device, whisper_frames(T)
+    r = torch.empty((rows, F, WHISPER_P + 1), device=dev, dtype=torch.float64)
+    check(lib.segan_whisper_lags(_ptr(x), _ptr(lens), _ptr(prev), _ptr(w), _ptr(g), rows, T,
+                                 _ptr(r), _stream()), 'whisper_lags')
+    res = whisper_lpc(r)
+    ws = torch.empty(rows * WHISPER_N * F, device=dev, dtype=torch.float64)
+    y = torch.empty((rows, T), device=dev, dtype=torch.float64)
+    prev_out = torch.empty(rows, device=dev, dtype=torch.float64)
+    peak = torch.empty(rows, device=dev, dtype=torch.float64)
+    status, nsilent, minorder = (torch.empty(rows, device=dev, dtype=torch.int32) for _ in range(3))
+    check(lib.segan_whisper_synth(_ptr(x), _ptr(lens), _ptr(prev), _ptr(r), _ptr(res['a']),
+                                  _ptr(res['sigma']), _ptr(res['order']), _ptr(s_d), _ptr(t_d),
+                                  _ptr(w), rows, T, _ptr(ws), ws.numel(), _ptr(y),
+                                  _RESAMPLE_DT[torch.float64], _ptr(prev_out), _ptr(peak),
+                                  _ptr(status), _ptr(nsilent), _ptr(minorder), _stream()),
+          'whisper_synth')
+    res.update(r=r, y64=y, prev64=prev_out, peak=peak, status=status, nsilent=nsilent,
+               minorder=minorder)
+    return res
+
+
+def whisper_rows(x, seeds, tilts, lengths=None, prev=None, out_dtype=None, lag_hz=120.0):
+    """Whispered copies of the rows of x [rows, T] (fp32 CUDA, 16 kHz): noise-excited LPC
+    resynthesis.  Frames of 512 at a hop of 256 under a periodic Hann window
+    keep their order-16 spectral envelope (lag window of `lag_hz`) and their energy; the
+    excitation is one continuous Philox noise sequence per row, seeds [rows] (host integers in 0 ..
+    2^63 - 1 or a CUDA int64 tensor), tilted by e = (u[j] - tau u[j-1]) / sqrt(1 + tau^2) with tau
+    = tilts [rows] in [0, 1): host numbers (anything else is refused here) or a CUDA float64 tensor
+    (a value outside then gives status WHISPER_TILT and the row unchanged).  lengths: host integers
+    or a CUDA int32 tensor; the output is zero from a row's length on.  prev (optional fp32 CUDA
+    [rows]): the sample preceding each row.  If the result's peak exceeds 1 the row is divided by
+    it.  out_dtype: torch.float32 (default; rounded once) or torch.float64.  Returns (y, info) with
+    info = dict(prev (y[-1], of out_dtype), status int32 [rows]: WHISPER_SILENT (every frame is
+    digital silence: unchanged) | WHISPER_TILT, nsilent int32 (silent frames), minorder int32 (the
+    lowest order the recursion reached), peak float64 (before the guard)).  No device-to-host
+    copy."""
+    rows, T, lens, s_d, t_d = _whisper_args('whisper_rows', x, seeds, tilts, lengths, prev)
+    out_dtype = _whisper_out_dtype('whisper_rows', out_dtype)
+    w, g = _whisper_tables(x.device, lag_hz)
+    lib = _lib.load()
+    dev = x.device
+    ws = _whisper_workspace(int(lib.segan_whisper_ws_doubles(rows, T)), dev)
+    y = torch.empty((rows, T), device=dev, dtype=out_dtype)
+    prev_out = torch.empty(rows, device=dev, dtype=out_dtype)
+    peak = torch.empty(rows, device=dev, dtype=torch.float64)
+    status, nsilent, minorder = (torch.empty(rows, device=dev, dtype=torch.int32) for _ in range(3))
+    check(lib.segan_whisper_rows(_ptr(x), _ptr(lens), _ptr(prev), _ptr(s_d), _ptr(t_d), _ptr(w),
+                                 _ptr(g), rows, T, _ptr(ws), ws.numel(), _ptr(y),
+                                 _RESAMPLE_DT[out_dtype], _ptr(prev_out), _ptr(peak), _ptr(status),
+                                 _ptr(nsilent), _ptr(minorder), _stream()), 'whisper_rows')
+    return y, dict(prev=prev_out, status=status, nsilent=nsilent, minorder=minorder, peak=peak)
+
+
 def rmsprop_step(p, g, sq, lr, alpha, eps):
     check(_lib.load().segan_rmsprop_step(_ptr(p), _ptr(g), _ptr(sq), lr, alpha, eps, p.numel(),
                                          _stream()), 'rmsprop_step')

@@ -16,7 +16,10 @@ responses, `--reverb_resample` converts responses that are not 16 kHz; with `--d
 each selected item (`--distort_prob`) is then clipped, has chunks of speech removed or is band
 limited on the GPU, one kind per item drawn from `clip chop bandlimit`: `--clip_factors`,
 `--chop_max`, `--chop_durs LO HI` and `--bandlimit_cutoffs` set the kinds' parameters, and
-'_clip' / '_chop' / '_bandlimit' is appended to the item's name), and under
+'_clip' / '_chop' / '_bandlimit' is appended to the item's name; with `--whisper` each selected
+item (`--whisper_prob`) is first of all turned into pseudo-whisper on the GPU by noise-excited LPC
+resynthesis, with a spectral tilt drawn from `--whisper_tilts` and an envelope smoothed by
+`--whisper_lag_hz`, while the clean, voiced slice stays the target), and under
 torch.distributed.run every
 rank trains on its shard of each epoch with RCCL gradient averaging.
 """
@@ -47,6 +50,10 @@ BANDLIMIT_CUTOFFS = (1000.0, 2000.0, 4000.0)
 DISTORT_SRATE = 16000
 DISTORT_ZEROS = 32          # augment.lowpass_bank: K = ceil(zeros srate / (2 fc)) taps a side
 DISTORT_MAX_K = 2048        # ops.FIR_MAX_K
+# the defaults of --whisper (augment.Whisper)
+WHISPER_TILTS = (0.0, 0.5, 0.9)
+WHISPER_LAG_HZ = 120.0
+WHISPER_MAX_LAG_HZ = 1000.0
 
 # (flag, kwargs) — names and defaults are the reference's (train.py:101-247)
 FLAGS = [
@@ -213,6 +220,21 @@ FLAGS = [
     ('--bandlimit_cutoffs', dict(type=float, nargs='+', default=list(BANDLIMIT_CUTOFFS),
                                  help='with --distort bandlimit: low-pass cutoffs in Hz, drawn '
                                       'uniformly per item')),
+    ('--whisper', dict(action='store_true', default=False,
+                       help='with --pcm_shard: each selected item is turned into pseudo-whisper on '
+                            'the GPU (noise-excited LPC resynthesis: the spectral envelope and the '
+                            'energy of every frame stay, the voiced excitation becomes noise) '
+                            'before any reverberation, distortion or noise; the clean slice stays '
+                            'the target and \'_whisper\' is appended to the utterance name')),
+    ('--whisper_prob', dict(type=float, default=1.0,
+                            help='probability that an item is whispered')),
+    ('--whisper_tilts', dict(type=float, nargs='+', default=list(WHISPER_TILTS),
+                             help='with --whisper: spectral tilts of the noise excitation in [0, 1) '
+                                  '(0: white; 0.9: nearly +6 dB per octave), drawn uniformly per '
+                                  'item')),
+    ('--whisper_lag_hz', dict(type=float, default=WHISPER_LAG_HZ,
+                              help='with --whisper: width in Hz of the lag window that smooths the '
+                                   'spectral envelope (0 .. 1000)')),
 ]
 
 
@@ -227,18 +249,35 @@ def _prob_in_range(flag, prob):
         raise SystemExit('{} must lie in 0 .. 1, got {}'.format(flag, prob))
 
 
+def _refuse_orphans(orphans):
+    """orphans: (moved, message) pairs, `moved` true when a sub-flag was given without the flag it
+    belongs to; the first such pair exits with its message."""
+    for moved, message in orphans:
+        if moved:
+            raise SystemExit(message)
+
+
+def _stage_on(opts, on, flag, does, orphans=()):
+    """What the check_*_flags of the loader's stages share.  A stage that is off tolerates none of
+    its sub-flags (`orphans`) and yields False; one that is on needs --pcm_shard."""
+    if not on:
+        _refuse_orphans(orphans)
+        return False
+    _needs_pcm_shard(opts, flag, does)
+    return True
+
+
 def check_additive_flags(opts):
     """The --additive_* flags go together with --pcm_shard; anything else exits with a message."""
     noises = getattr(opts, 'additive_noises', None)
     snrs = list(getattr(opts, 'additive_snrs', [0, 5, 10]))
     prob = getattr(opts, 'additive_prob', 1.0)
-    if noises is None:
-        if snrs != [0, 5, 10] or prob != 1.0:
-            raise SystemExit('--additive_snrs / --additive_prob need --additive_noises DIR')
-        if getattr(opts, 'additive_resample', False):
-            raise SystemExit('--additive_resample needs --additive_noises DIR')
+    if not _stage_on(opts, noises is not None, '--additive_noises', 'mixes noise into', (
+            (snrs != [0, 5, 10] or prob != 1.0,
+             '--additive_snrs / --additive_prob need --additive_noises DIR'),
+            (getattr(opts, 'additive_resample', False),
+             '--additive_resample needs --additive_noises DIR'))):
         return False
-    _needs_pcm_shard(opts, '--additive_noises', 'mixes noise into')
     _prob_in_range('--additive_prob', prob)
     if len(snrs) == 0:
         raise SystemExit('--additive_snrs needs at least one level')
@@ -250,13 +289,12 @@ def check_reverb_flags(opts):
     rirs = getattr(opts, 'reverb_rirs', None)
     prob = getattr(opts, 'reverb_prob', 1.0)
     max_taps = getattr(opts, 'reverb_max_taps', 16384)
-    if rirs is None:
-        if prob != 1.0 or max_taps != 16384:
-            raise SystemExit('--reverb_prob / --reverb_max_taps need --reverb_rirs DIR')
-        if getattr(opts, 'reverb_resample', False):
-            raise SystemExit('--reverb_resample needs --reverb_rirs DIR')
+    if not _stage_on(opts, rirs is not None, '--reverb_rirs', 'reverberates', (
+            (prob != 1.0 or max_taps != 16384,
+             '--reverb_prob / --reverb_max_taps need --reverb_rirs DIR'),
+            (getattr(opts, 'reverb_resample', False),
+             '--reverb_resample needs --reverb_rirs DIR'))):
         return False
-    _needs_pcm_shard(opts, '--reverb_rirs', 'reverberates')
     _prob_in_range('--reverb_prob', prob)
     if max_taps < 1:
         raise SystemExit('--reverb_max_taps must be positive, got {}'.format(max_taps))
@@ -274,17 +312,16 @@ def check_distort_flags(opts):
     durs = list(getattr(opts, 'chop_durs', CHOP_DURS))
     cutoffs = list(getattr(opts, 'bandlimit_cutoffs', BANDLIMIT_CUTOFFS))
     kinds = [] if kinds is None else list(kinds)
-    if not kinds and prob != 1.0:
-        raise SystemExit('--distort_prob needs --distort KIND [KIND ...]')
-    if 'clip' not in kinds and factors != list(CLIP_FACTORS):
-        raise SystemExit('--clip_factors needs --distort clip')
-    if 'chop' not in kinds and (chop_max != CHOP_MAX or durs != list(CHOP_DURS)):
-        raise SystemExit('--chop_max / --chop_durs need --distort chop')
-    if 'bandlimit' not in kinds and cutoffs != list(BANDLIMIT_CUTOFFS):
-        raise SystemExit('--bandlimit_cutoffs needs --distort bandlimit')
-    if not kinds:
+    _refuse_orphans((      # a kind's sub-flags are orphans also when another kind is on
+        (not kinds and prob != 1.0, '--distort_prob needs --distort KIND [KIND ...]'),
+        ('clip' not in kinds and factors != list(CLIP_FACTORS),
+         '--clip_factors needs --distort clip'),
+        ('chop' not in kinds and (chop_max != CHOP_MAX or durs != list(CHOP_DURS)),
+         '--chop_max / --chop_durs need --distort chop'),
+        ('bandlimit' not in kinds and cutoffs != list(BANDLIMIT_CUTOFFS),
+         '--bandlimit_cutoffs needs --distort bandlimit')))
+    if not _stage_on(opts, bool(kinds), '--distort', 'distorts'):
         return False
-    _needs_pcm_shard(opts, '--distort', 'distorts')
     if len(set(kinds)) != len(kinds):
         raise SystemExit('--distort names a kind twice: {}'.format(' '.join(kinds)))
     _prob_in_range('--distort_prob', prob)
@@ -308,6 +345,25 @@ def check_distort_flags(opts):
     return True
 
 
+def check_whisper_flags(opts):
+    """The --whisper flags go together with --pcm_shard, and the sub-flags with --whisper; anything
+    else exits with a message.  Host arithmetic only: nothing here touches a device."""
+    prob = getattr(opts, 'whisper_prob', 1.0)
+    tilts = list(getattr(opts, 'whisper_tilts', WHISPER_TILTS))
+    lag_hz = getattr(opts, 'whisper_lag_hz', WHISPER_LAG_HZ)
+    if not _stage_on(opts, bool(getattr(opts, 'whisper', False)), '--whisper', 'whispers', (
+            (prob != 1.0 or tilts != list(WHISPER_TILTS) or lag_hz != WHISPER_LAG_HZ,
+             '--whisper_prob / --whisper_tilts / --whisper_lag_hz need --whisper'),)):
+        return False
+    _prob_in_range('--whisper_prob', prob)
+    if len(tilts) == 0 or not all(0.0 <= t < 1.0 for t in tilts):
+        raise SystemExit('--whisper_tilts must lie in [0, 1), got {}'.format(tilts))
+    if not 0.0 <= lag_hz <= WHISPER_MAX_LAG_HZ:
+        raise SystemExit('--whisper_lag_hz must lie in 0 .. {} Hz, got {}'.format(
+            int(WHISPER_MAX_LAG_HZ), lag_hz))
+    return True
+
+
 def build_parser():
     p = argparse.ArgumentParser(description=__doc__,
                                 formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -320,6 +376,7 @@ def main(opts):
     use_additive = check_additive_flags(opts)
     use_reverb = check_reverb_flags(opts)
     use_distort = check_distort_flags(opts)
+    use_whisper = check_whisper_flags(opts)
     if getattr(opts, 'sync_bn', False):
         os.environ['SEGAN_SYNC_BN'] = '1'
     rank, world, local = sdist.init_from_env()
@@ -398,6 +455,10 @@ def main(opts):
                     'bandlimit': lambda: augment.BandLimit(opts.bandlimit_cutoffs, DISTORT_SRATE,
                                                            DISTORT_ZEROS)}
             distort = augment.Distort({k: make[k]() for k in opts.distort})
+        whisper = None
+        if use_whisper:
+            from segan_pytorch_amd.augment import Whisper
+            whisper = Whisper(opts.whisper_tilts, opts.whisper_lag_hz)
         dloader = PCMShardLoader(dset, opts.batch_size, opts.preemph, device, sampler=sampler,
                                  drop_last=(world > 1), num_workers=max(1, min(2, opts.num_workers)),
                                  additive=additive, additive_prob=opts.additive_prob,
@@ -408,7 +469,9 @@ def main(opts):
                                  # same uniforms
                                  reverb_seed=[opts.seed + rank, 1],
                                  distort=distort, distort_prob=opts.distort_prob,
-                                 distort_seed=[opts.seed + rank, 2])
+                                 distort_seed=[opts.seed + rank, 2],
+                                 whisper=whisper, whisper_prob=opts.whisper_prob,
+                                 whisper_seed=[opts.seed + rank, 3])
     else:
         dloader = DataLoader(dset, batch_size=opts.batch_size, shuffle=(sampler is None),
                              sampler=sampler, num_workers=workers, pin_memory=pin,
