@@ -17,7 +17,6 @@ checked against them on a machine without a GPU.
 
 Transform subsets are spelled with the letters c (scale), h (shift), l (slope).
 """
-import functools
 import types
 import zlib
 
@@ -449,6 +448,9 @@ def deconv64(x, w, b, S):
     return y[:, :, :S * x.shape[2]]
 
 
+_CACHE = {}      # (id of the case object, exact leg) -> what inputs() returns
+
+
 def _grad(fn, shape, cot):
     """The adjoint of the linear map fn at `cot`, in fp64."""
     with torch.enable_grad():
@@ -457,9 +459,8 @@ def _grad(fn, shape, cot):
     return g
 
 
-@functools.lru_cache(maxsize=None)
-def _inputs(kind, name, exact):
-    c = next(c for c in TABLES[kind] if c.name == name)
+def _build(c, exact):
+    kind = c.kind
     g = _gen(c, 'exact' if exact else 'random')
     i = ns(case=c, exact=exact)
     ab = torch.abs
@@ -515,8 +516,12 @@ def _inputs(kind, name, exact):
 
 def inputs(c, exact=True):
     """CPU inputs, the fp64 reference and the exactness bound of a case; computed once per case and
-    leg and shared: callers must leave them unchanged."""
-    return _inputs(c.kind, c.name, bool(exact))
+    leg (the case objects are module-level tables, here or in another sweep's module, and live as
+    long as the cache) and shared: callers must leave them unchanged."""
+    key = (id(c), bool(exact))
+    if key not in _CACHE:
+        _CACHE[key] = _build(c, bool(exact))
+    return _CACHE[key]
 
 
 def check_exact(c):
