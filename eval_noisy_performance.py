@@ -3,7 +3,7 @@ the clean wavs of the same names, on the MI355X: the reference's eval_noisy_perf
 
     python eval_noisy_performance.py --test_wavs DIR --clean_wavs DIR --logfile FILE [--stoi]
                                      [--estoi] [--fwsegsnr] [--cd] [--sisdr] [--sdr] [--srmr]
-                                     [--resample]
+                                     [--f0] [--resample]
 
 16 kHz wavs only (int16 files are scaled by 1/32768, float files used as they are), unless
 --resample converts files of other rates to 16 kHz on the GPU first (int16 files to int16, float
@@ -18,7 +18,10 @@ in dB) with their final mean lines; none of the three needs pesqmain.  --sdr add
 column SDR (quality.sdr, the BSS-eval signal-to-distortion ratio in dB with a 512-tap distortion
 filter) and its mean line.  --srmr adds, last, the column SRMR (quality.srmr, the
 speech-to-reverberation modulation energy ratio of the degraded file alone: it needs no clean
-signal) and its mean line."""
+signal) and its mean line.  --f0 adds, after every other column, F0MAE, VUV and F0KLD
+(quality.f0_eval: the F0 mean absolute error in Hz, the voiced / unvoiced accuracy and the KL
+divergence between the log-F0 distributions, on YIN contours tracked on the GPU) and, for each, a
+final mean line over the files where it is finite with the count of NaN files."""
 import argparse
 import glob
 import os
@@ -61,11 +64,14 @@ EXTRA = (('STOI', 'stoi', 'stoi'), ('ESTOI', 'estoi', 'estoi'),
          ('FWSEGSNR', 'fwsegsnr', 'fwsegsnr'), ('CD', 'cd', 'cepstral_distance'),
          ('SISDR', 'sisdr', 'si_sdr'), ('SDR', 'sdr', 'sdr'), ('SRMR', 'srmr', 'srmr'))
 BLIND = ('SRMR',)     # columns computed on the degraded file alone
+# the columns of --f0, after every column of EXTRA: (column, key of quality.f0_eval's dict)
+F0_COLUMNS = (('F0MAE', 'f0_mae'), ('VUV', 'vuv_acc'), ('F0KLD', 'f0_kld'))
 
 
 def header_line(opts):
     return 'FILE CSIG CBAK COVL PESQ SSNR' + ''.join(
-        ' ' + name for name, flag, _ in EXTRA if getattr(opts, flag))
+        ' ' + name for name, flag, _ in EXTRA if getattr(opts, flag)) + ''.join(
+            ' ' + name for name, _ in F0_COLUMNS if getattr(opts, 'f0', False))
 
 
 def main(opts):
@@ -78,6 +84,8 @@ def main(opts):
     noisy_wavs = sorted(glob.glob(os.path.join(opts.test_wavs, '*.wav')))
     metrics = {'csig': [], 'cbak': [], 'covl': [], 'STOI': [], 'ESTOI': [], 'FWSEGSNR': [],
                'CD': [], 'SISDR': [], 'SDR': [], 'SRMR': []}
+    with_f0 = bool(getattr(opts, 'f0', False))
+    f0_rows = {name: [] for name, _ in F0_COLUMNS}
     timings = []
     with open(opts.logfile, 'w') as out_log:
         out_log.write(header_line(opts) + '\n')
@@ -98,6 +106,12 @@ def main(opts):
                         metrics[name].append(float(fn(torch.from_numpy(noisy).cuda())[0]))
                     else:
                         metrics[name].append(float(fn(c, d)[0]))
+            if with_f0:
+                L = min(len(clean), len(noisy))
+                f0r = quality.f0_eval(torch.from_numpy(clean[:L]).cuda(),
+                                      torch.from_numpy(noisy[:L]).cuda())
+                for name, key in F0_COLUMNS:
+                    f0_rows[name].append(float(f0r[key][0]))
             end_t = timeit.default_timer()
             timings.append(end_t - beg_t)
             metrics['csig'].append(csig)
@@ -105,7 +119,9 @@ def main(opts):
             metrics['covl'].append(covl)
             out_log.write('{} {:.3f} {:.3f} {:.3f} {:.3f} {:.3}'.format(bname + '.wav', csig,
                                                                         cbak, covl, pesq, ssnr) +
-                          ''.join(' {:.4f}'.format(metrics[name][-1]) for name, _ in extra) + '\n')
+                          ''.join(' {:.4f}'.format(metrics[name][-1]) for name, _ in extra) +
+                          ''.join(' {:.4f}'.format(f0_rows[name][-1]) for name, _ in F0_COLUMNS
+                                  if with_f0) + '\n')
             print('Processed {}/{} wav, CSIG:{:.3f} CBAK:{:.3f} COVL:{:.3f} '
                   'PESQ:{:.3f} SSNR:{:.3f} '
                   'total time: {:.2f} seconds, mproc: {:.2f}'
@@ -116,6 +132,12 @@ def main(opts):
     print('mean Covl: ', np.mean(metrics['covl']))
     for name, _ in extra:
         print('mean {}: '.format(name), np.mean(metrics[name]))
+    if with_f0:
+        for name, _ in F0_COLUMNS:
+            v = np.asarray(f0_rows[name], dtype=np.float64)
+            fin = v[np.isfinite(v)]
+            print('mean {}: '.format(name), fin.mean() if len(fin) else float('nan'),
+                  '({} NaN of {} files)'.format(len(v) - len(fin), len(v)))
 
 
 def build_parser():
@@ -140,6 +162,10 @@ def build_parser():
     parser.add_argument('--srmr', action='store_true', default=False,
                         help='also compute SRMR (speech-to-reverberation modulation energy ratio '
                              'of the degraded file alone)')
+    parser.add_argument('--f0', action='store_true', default=False,
+                        help='also compute F0MAE, VUV and F0KLD (F0 mean absolute error in Hz, '
+                             'voiced / unvoiced accuracy, KL divergence of the log-F0 '
+                             'distributions) on YIN pitch contours')
     parser.add_argument('--resample', action='store_true', default=False,
                         help='convert wavs that are not 16 kHz to 16 kHz on the GPU instead of '
                              'refusing them')

@@ -546,6 +546,48 @@ int segan_fft_z2z(const double* in, double* out, int rows, int log2n, int invers
 int segan_srmr_dims(int rows, int T, int rate, long long* out);
 int segan_srmr(const float* x, const int* lengths, int rows, int T, int rate, double* row_out,
                double* stages_out, double* ws, void* stream);
+/* Pitch tracking by YIN (de Cheveigne & Kawahara 2002) with a 5 ms hop, and the F0 / voicing
+ * measures on two such contours; DESIGN.md section 19, scripts/pitch_oracle.py.  fp64 on fp32 rows
+ * x [rows][T] at `srate` (16000 or 8000), row r restricted to its first lengths[r] = L samples
+ * (device int[rows], clamped to 0 .. T; NULL: all T).  At 16 kHz H = 80, tau_min = 40, tau_max =
+ * 266 (8 kHz: all halved), NB = SEGAN_PITCH_NB hop blocks per frame:
+ *   hop blocks u < nb = (L - (tau_max + 1)) / H (0 below that): S_u(tau) = sum x[j] x[j+tau],
+ *     E_u(tau) = sum x[j+tau]^2 over j in [uH, uH + H) ascending, tau = 0 .. tau_max + 1 (exact
+ *     products);
+ *   frames t < nf = nb - NB + 1 (0 below that): the blocks t .. t + NB - 1 added in ascending
+ *     order; d(0) = 0, d(tau) = (E(0) + E(tau)) - 2 R(tau); c(tau) the ascending running sum of
+ *     d(1 .. tau); d'(tau) = d(tau) tau / c(tau) where c(tau) > 0, else 1;
+ *   the pick: the smallest tau in [tau_min, tau_max] with d'(tau) < theta, then onwards while
+ *     tau < tau_max and d'(tau + 1) < d'(tau); none, or c(tau_max + 1) not > 0: unvoiced;
+ *   f0 = srate / (tau + delta), delta = clamp(0.5 (a - c) / (a - 2 b + c), -0.5, 0.5) with
+ *     a, b, c = d' at tau - 1, tau, tau + 1 (0 where the denominator is not > 0).
+ *   segan_pitch_frames (host only): nf of a row of T samples, -1 for a bad argument.
+ *   segan_pitch_dims (host only): out[6] = {H, tau_min, tau_max, nb of T, F = nf of T, the doubles
+ *     of workspace `ws` for `rows` rows}.
+ *   segan_pitch: f0 [rows][F] (0 when unvoiced), lag int[rows][F] (0 when unvoiced), ap [rows][F]
+ *     (d' at the pick; the minimum of d' over [tau_min, tau_max] when unvoiced); frames from the
+ *     row's own nf on: f0 = 0, lag = -1, ap = NaN.  theta in (0, 1].  F == 0: nothing is written.
+ *   segan_pitch_cmnd: d' itself, cmnd [rows][F][tau_max + 2] (NaN from the row's own nf on).
+ *   segan_f0_eval: f0 / lag [rows][F] of the clean and the processed contour, nframes int[rows]
+ *     (device, clamped to 0 .. F; NULL: F), F >= 0; out4 [rows][4] = (f0_mae in Hz over the clean
+ *     contour's voiced frames, vuv_acc, f0_kld between the log-f0 distributions, voiced), on the
+ *     log-f0 contours interpolated linearly over the unvoiced frames, every sum in ascending frame
+ *     order.  NaN: all four without a frame; f0_mae and f0_kld where either contour has no voiced
+ *     frame; f0_kld below two frames or with a constant processed contour.
+ * No atomics, every sum in an order fixed by the indices: a row's bits depend neither on T, nor on
+ * the other rows, nor on the samples past its length, and a row times a power of two gives the
+ * same lags and f0 bits.  rows in 1 .. 65535, T in 1 .. 2^24, checked before any launch.  Added
+ * without a change of SEGAN_ABI_VERSION: the exports are purely additive. */
+#define SEGAN_PITCH_NB 5
+int segan_pitch_frames(int T, int srate);
+int segan_pitch_dims(int rows, int T, int srate, long long* out);
+int segan_pitch(const float* x, const int* lengths, int rows, int T, int srate, double theta,
+                double* f0, int* lag, double* ap, double* ws, void* stream);
+int segan_pitch_cmnd(const float* x, const int* lengths, int rows, int T, int srate, double* cmnd,
+                     double* ws, void* stream);
+int segan_f0_eval(const double* f0_ref, const int* lag_ref, const double* f0_deg,
+                  const int* lag_deg, const int* nframes, int rows, int F, double* out4,
+                  void* stream);
 
 /* ---- on-the-fly additive noise (the reference's Additive, utils.py:43-297)
  * fp64 arithmetic on fp32 rows x / clean [rows][T], row r restricted to its first lengths[r]

@@ -17,6 +17,11 @@ utterance like eval_noisy_performance.py, with a device synchronise; prints one 
         # signals of the same set (ops.srmr chunks it under its workspace cap), and the numpy /
         # scipy oracle scripts/srmr_oracle.py on --srmr-cpu of its utterances; the JSON line also
         # goes to --srmr-out (profiles/srmr_bench.json)
+    python scripts/bench_quality.py --pitch      # instead: ONE call each of quality.pitch over the
+        # degraded signals and of quality.f0_eval (two trackings and the measures) over the same
+        # set with a harmonic glide added to every utterance, and the numpy oracle
+        # scripts/pitch_oracle.py on --pitch-cpu of its utterances; the JSON line also goes to
+        # --pitch-out (profiles/pitch_bench.json)
 """
 import argparse
 import ctypes
@@ -59,8 +64,20 @@ def main():
                     help='time the batched SRMR call and its numpy / scipy oracle instead')
     ap.add_argument('--srmr-cpu', type=int, default=3)
     ap.add_argument('--srmr-out', default=os.path.join(ROOT, 'profiles', 'srmr_bench.json'))
+    ap.add_argument('--pitch', action='store_true',
+                    help='time the batched pitch tracking and F0 measures and their numpy oracle '
+                         'instead')
+    ap.add_argument('--pitch-cpu', type=int, default=3)
+    ap.add_argument('--pitch-out', default=os.path.join(ROOT, 'profiles', 'pitch_bench.json'))
     args = ap.parse_args()
     utts = utterances()
+    if args.pitch:
+        import torch
+        out = batched_pitch(torch, utts, args.batch_reps, args.pitch_cpu)
+        with open(args.pitch_out, 'w') as f:
+            f.write(json.dumps(out) + '\n')
+        print(json.dumps(out))
+        return
     if args.srmr:
         import torch
         out = batched_srmr(torch, utts, args.batch_reps, args.srmr_cpu)
@@ -227,6 +244,65 @@ def batched_srmr(torch, utts, reps, ncpu):
             'oracle_cpu_utts': ncpu, 'oracle_cpu_s_per_utt': cpu,
             'max_rel_diff_vs_oracle': max([abs(a - b) / abs(b) for a, b in zip(got, want)]
                                           or [0.0])}
+
+
+def batched_pitch(torch, utts, reps, ncpu):
+    """Seconds of one quality.pitch call over the degraded signals of the whole set and of one
+    quality.f0_eval call over the pairs (after one warm-up call each, mean of `reps`, up to a
+    device synchronise; ops.pitch walks the rows in chunks under its workspace cap), with a
+    harmonic glide added to every utterance so that there is a pitch to find; the oracle's seconds
+    per utterance (two trackings and the measures) on the first `ncpu` utterances, whether every
+    lag agrees on those, and the largest difference in f0_mae."""
+    sys.path.insert(0, os.path.join(ROOT, 'scripts'))
+    import pitch_oracle
+    from segan_pytorch_amd import ops, quality
+    rng = np.random.default_rng(1)
+    pairs = []
+    for c, d in utts:
+        f0 = np.geomspace(rng.uniform(80, 200), rng.uniform(100, 300), len(c))
+        h = np.sin(2 * np.pi * np.cumsum(f0) / 16000).astype(np.float32)
+        pairs.append((c * np.float32(0.1) + h, d * np.float32(0.3) + h))
+    lengths = [len(c) for c, _ in pairs]
+    ref = torch.zeros(len(pairs), max(lengths))
+    deg = torch.zeros(len(pairs), max(lengths))
+    for i, (c, d) in enumerate(pairs):
+        ref[i, :len(c)] = torch.from_numpy(c)
+        deg[i, :len(d)] = torch.from_numpy(d)
+    ref, deg = ref.cuda(), deg.cuda()
+
+    def timed(fn):
+        out = fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            out = fn()
+        torch.cuda.synchronize()
+        return out, (time.perf_counter() - t0) / reps
+
+    (f0, voiced, _), dt_pitch = timed(lambda: quality.pitch(deg, lengths=lengths))
+    ev, dt_eval = timed(lambda: quality.f0_eval(ref, deg, lengths=lengths))
+    per_row = 8 * ops.pitch_dims(1, max(lengths))['ws_doubles']
+    t0 = time.perf_counter()
+    want = [(pitch_oracle.track(c), pitch_oracle.track(d)) for c, d in pairs[:ncpu]]
+    want_ev = [pitch_oracle.f0_eval(a['f0'], a['lag'], b['f0'], b['lag']) for a, b in want]
+    cpu = (time.perf_counter() - t0) / max(ncpu, 1)
+    same = all(np.array_equal(b['lag'] > 0, voiced[i, :len(b['lag'])].cpu().numpy())
+               for i, (_, b) in enumerate(want))
+    mae = ev['f0_mae']
+    return {'leg': 'mi355x', 'measure': 'pitch', 'utts': len(pairs),
+            'mean_audio_s': float(np.mean(lengths)) / 16000, 'frames': int(f0.shape[1]),
+            'pitch_seconds': dt_pitch, 'pitch_utts_per_s': len(pairs) / dt_pitch,
+            'f0_eval_seconds': dt_eval, 'f0_eval_utts_per_s': len(pairs) / dt_eval,
+            'ws_cap_bytes': ops.PITCH_WS_CAP, 'ws_bytes_per_row': per_row,
+            'calls': -(-len(pairs) // max(1, ops.PITCH_WS_CAP // per_row)),
+            'mean_voiced_share': float(ev['voiced'].mean()),
+            'mean_f0_mae': float(mae[torch.isfinite(mae)].mean()),
+            'f0_mae_nonfinite_rows': int((~torch.isfinite(mae)).sum()),
+            'mean_vuv_acc': float(ev['vuv_acc'].mean()),
+            'oracle_cpu_utts': ncpu, 'oracle_cpu_s_per_utt_pair': cpu,
+            'voicing_same_as_oracle': bool(same),
+            'max_abs_diff_f0_mae_vs_oracle': max(
+                [abs(float(mae[i]) - float(w['f0_mae'])) for i, w in enumerate(want_ev)] or [0.0])}
 
 
 if __name__ == '__main__':

@@ -109,6 +109,11 @@ SIGNATURES = {
     'segan_fft_z2z': (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     'segan_srmr_dims': (c_int, [c_int, c_int, c_int, POINTER(c_int64)]),
     'segan_srmr': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P]),
+    'segan_pitch_frames': (c_int, [c_int, c_int]),
+    'segan_pitch_dims': (c_int, [c_int, c_int, c_int, POINTER(c_int64)]),
+    'segan_pitch': (c_int, [_P, _P, c_int, c_int, c_int, c_double, _P, _P, _P, _P, _P]),
+    'segan_pitch_cmnd': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P]),
+    'segan_f0_eval': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, _P]),
     'segan_asl_p56': (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     'segan_additive_mix': (c_int, [_P, _P, _P, c_int64, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P]),
     'segan_resample_plan': (c_int, [c_int, c_int, c_int, c_double, POINTER(c_int), POINTER(c_int), _P, c_int]),

@@ -427,7 +427,10 @@ class SEGAN(Model):
         'sisdr' (quality.fwsegsnr, quality.cepstral_distance, quality.si_sdr), and with
         `opts.eval_sdr` the key 'sdr' (quality.sdr, BSS-eval SDR with a 512-tap filter).  With
         `opts.eval_srmr` the key 'srmr' (quality.srmr) is the speech-to-reverberation modulation
-        energy ratio of the enhanced (noisy) signal alone: it uses no clean signal.
+        energy ratio of the enhanced (noisy) signal alone: it uses no clean signal.  With
+        `opts.eval_f0` (train.py --eval_f0) the keys 'f0_mae', 'vuv_acc', 'f0_kld' (quality.f0_eval:
+        F0 error in Hz, voiced / unvoiced accuracy and log-F0 KL divergence on YIN contours) are
+        added, computed on the same signals; a value is NaN where the measure is undefined.
         De-emphasis runs along time (the reference applies it along axis 0 of the [B, T] batch,
         model.py:474-477)."""
         from .. import ops, quality
@@ -440,9 +443,10 @@ class SEGAN(Model):
                                       ('sisdr', quality.si_sdr), ('sdr', quality.sdr))
                 if bool(getattr(opts, 'eval_' + k, False))]
         with_srmr = bool(getattr(opts, 'eval_srmr', False))
+        f0_keys = ('f0_mae', 'vuv_acc', 'f0_kld') if bool(getattr(opts, 'eval_f0', False)) else ()
         keys = ('ssnr', 'snr', 'pesq', 'csig', 'cbak', 'covl', 'wss', 'llr') + (
             ('stoi',) if with_stoi else ()) + (('estoi',) if with_estoi else ()) + tuple(
-                k for k, _ in more) + (('srmr',) if with_srmr else ())
+                k for k, _ in more) + (('srmr',) if with_srmr else ()) + f0_keys
         evals = {k: [] for k in keys}
         noisy_evals = {k: [] for k in keys}
         workers = getattr(opts, 'eval_workers', 2)
@@ -471,6 +475,10 @@ class SEGAN(Model):
                         dst[k] += fn(c, d).cpu().tolist()
                     if with_srmr:
                         dst['srmr'] += quality.srmr(d).cpu().tolist()
+                    if f0_keys:
+                        f0r = quality.f0_eval(c, d)
+                        for k in f0_keys:
+                            dst[k] += f0r[k].cpu().tolist()
                 if bidx >= max_samples:
                     break
         self.G.train()

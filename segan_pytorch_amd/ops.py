@@ -1436,6 +1436,124 @@ def srmr(x, lengths=None, rate=16000, ws_cap=SRMR_WS_CAP):
     return srmr_stages(x, lengths, rate, ws_cap)['srmr']
 
 
+PITCH_NB = 5             # SEGAN_PITCH_NB: hop blocks per frame
+PITCH_RATES = (8000, 16000)
+PITCH_THETA = 0.15       # YIN's threshold on the normalised difference
+PITCH_MAX_T = 1 << 24
+PITCH_WS_CAP = 1 << 30   # bytes of workspace one call of segan_pitch may take
+
+
+def pitch_dims(rows, T, srate=16000):
+    """segan_pitch_dims (host only) as a dict: hop, tau_min, tau_max, blocks and frames of a row
+    of T samples, ws_doubles for `rows` rows."""
+    dims = (ctypes.c_int64 * 6)()
+    check(_lib.load().segan_pitch_dims(rows, T, srate, dims), 'pitch')
+    return dict(zip(('hop', 'tau_min', 'tau_max', 'blocks', 'frames', 'ws_doubles'), list(dims)))
+
+
+def _pitch_run(x, lengths, srate, threshold, ws_cap, want_cmnd):
+    _chk(x, 'x', 2)
+    rows, T = x.shape
+    if not 1 <= rows <= 65535 or not 1 <= T <= PITCH_MAX_T:
+        raise ValueError('pitch: 1 .. 65535 rows of 1 .. 2^24 samples, got {}'.format(
+            tuple(x.shape)))
+    if isinstance(srate, bool) or srate not in PITCH_RATES:
+        raise ValueError('pitch: srate must be one of {}, got {!r}'.format(PITCH_RATES, srate))
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or not (
+            0 < threshold <= 1):
+        raise ValueError('pitch: threshold must lie in (0, 1], got {!r}'.format(threshold))
+    lens = None if lengths is None else _row_lengths('pitch', lengths, rows, T, x.device)
+    cap = _int_arg(ws_cap, 'pitch: ws_cap', 1, 1 << 62)
+    lib = _lib.load()
+    d = pitch_dims(1, T, srate)
+    F, nl = d['frames'], d['tau_max'] + 2
+    per = int(cap // max(8 * d['ws_doubles'], 1))
+    if per < 1:
+        raise ValueError('pitch: ws_cap of {} bytes is below the {} bytes one row of {} samples '
+                         'needs'.format(cap, 8 * d['ws_doubles'], T))
+    per = min(per, rows)
+    ws = _stream_scratch(max(8 * d['ws_doubles'] * per, 8), x.device)
+    f64 = dict(device=x.device, dtype=torch.float64)
+    f0 = torch.empty((rows, max(F, 1)), **f64)
+    ap = torch.empty((rows, max(F, 1)), **f64)
+    lag = torch.empty((rows, max(F, 1)), device=x.device, dtype=torch.int32)
+    cm = torch.empty((rows, max(F, 1), nl), **f64) if want_cmnd else None
+    for r0 in range(0, rows, per):
+        n = min(per, rows - r0)
+        xs, ls = x[r0:r0 + n], _ptr(None if lens is None else lens[r0:r0 + n])
+        check(lib.segan_pitch(_ptr(xs), ls, n, T, srate, float(threshold), _ptr(f0[r0:r0 + n]),
+                              _ptr(lag[r0:r0 + n]), _ptr(ap[r0:r0 + n]), _ptr(ws), _stream()),
+              'pitch')
+        if want_cmnd:
+            check(lib.segan_pitch_cmnd(_ptr(xs), ls, n, T, srate, _ptr(cm[r0:r0 + n]), _ptr(ws),
+                                       _stream()), 'pitch_cmnd')
+    if lens is None:
+        nframes = torch.full((rows,), F, device=x.device, dtype=torch.int32)
+    else:
+        host = lens.cpu().tolist()
+        nframes = torch.tensor([lib.segan_pitch_frames(L, srate) for L in host],
+                               dtype=torch.int32).to(x.device)
+    out = {'f0': f0[:, :F], 'lag': lag[:, :F], 'ap': ap[:, :F], 'nframes': nframes}
+    if want_cmnd:
+        out['cmnd'] = cm[:, :F]
+    return out
+
+
+def pitch_stages(x, lengths=None, srate=16000, threshold=PITCH_THETA, ws_cap=PITCH_WS_CAP):
+    """`pitch` with its intermediate as a dict of device tensors: 'f0',
+    'lag', 'ap' [rows, F], 'nframes' [rows] (int32: each row's own frame count) and 'cmnd'
+    [rows, F, tau_max + 2], YIN's cumulative-mean-normalised difference d' of every frame and lag
+    (NaN from the row's own frame count on)."""
+    return _pitch_run(x, lengths, srate, threshold, ws_cap, True)
+
+
+def pitch(x, lengths=None, srate=16000, threshold=PITCH_THETA, ws_cap=PITCH_WS_CAP):
+    """The pitch contour of each row of x [rows, T] (fp32 CUDA tensor) at `srate` (16000 or 8000)
+    by YIN with a 5 ms hop on the device, fp64: (f0 [rows, F] in Hz, 0 when unvoiced; lag [rows, F]
+    int32, the period picked in samples, 0 when unvoiced; ap [rows, F], d' at the pick or its
+    minimum over the lag range when unvoiced; nframes [rows] int32).  A frame is 25 ms, lags run
+    from srate / 400 to srate / 60.2; `threshold` in (0, 1].  Row r is x[r, :lengths[r]] (host
+    integers 0 .. T; all T without `lengths`); frames from the row's own count on hold f0 = 0,
+    lag = -1, ap = NaN.  The rows are processed in chunks whose workspace stays under `ws_cap`
+    bytes.  Fixed operation order: a batched row equals its own call bit for bit, and a row times
+    a power of two gives the same lags and f0 bits."""
+    out = _pitch_run(x, lengths, srate, threshold, ws_cap, False)
+    return out['f0'], out['lag'], out['ap'], out['nframes']
+
+
+def f0_eval(f0_ref, lag_ref, f0_deg, lag_deg, nframes=None):
+    """The F0 / voicing measures of the reference (ops.py:51-260 there) on the contours of a clean
+    and a processed signal (`pitch`'s f0 fp64 and lag int32, [rows, F] CUDA tensors; `nframes`:
+    int32 CUDA [rows], each row's frame count, all F without it): fp64 [rows, 4] = (f0_mae, the
+    mean |f0 difference| in Hz over the clean contour's voiced frames; vuv_acc, the share of
+    frames with the same voicing decision; f0_kld, the KL divergence between the Gaussian fits of
+    the two log-f0 distributions; voiced, the clean contour's share of voiced frames), on the
+    log-f0 contours interpolated linearly over the unvoiced frames.  NaN: all four without a
+    frame; f0_mae and f0_kld where either contour has no voiced frame; f0_kld below two frames or
+    for a constant processed contour."""
+    _chk(f0_ref, 'f0_ref', 2, torch.float64)
+    _chk(f0_deg, 'f0_deg', 2, torch.float64)
+    _chk(lag_ref, 'lag_ref', 2, torch.int32)
+    _chk(lag_deg, 'lag_deg', 2, torch.int32)
+    if not f0_ref.shape == lag_ref.shape == f0_deg.shape == lag_deg.shape:
+        raise ValueError('f0_eval: shapes differ: {}'.format(
+            [tuple(t.shape) for t in (f0_ref, lag_ref, f0_deg, lag_deg)]))
+    rows, F = f0_ref.shape
+    if not 1 <= rows <= 65535:
+        raise ValueError('f0_eval: 1 .. 65535 rows, got {}'.format(rows))
+    if nframes is not None:
+        _chk(nframes, 'nframes', 1, torch.int32)
+        if nframes.shape != (rows,):
+            raise ValueError('f0_eval: nframes must be int32 [{}]'.format(rows))
+    out = torch.empty((rows, 4), device=f0_ref.device, dtype=torch.float64)
+    if F == 0:      # an empty tensor has no address; the kernel reads nothing and writes NaN
+        f0_ref = f0_deg = out
+        lag_ref = lag_deg = torch.empty(1, device=out.device, dtype=torch.int32)
+    check(_lib.load().segan_f0_eval(_ptr(f0_ref), _ptr(lag_ref), _ptr(f0_deg), _ptr(lag_deg),
+                                    _ptr(nframes), rows, F, _ptr(out), _stream()), 'f0_eval')
+    return out
+
+
 ASL_THRESHOLDS = 15      # nbits - 1 thresholds 2^-15 .. 2^-1 (nbits = 16)
 ADDITIVE_CAP = 1         # status bits of asl_p56 / additive_mix (include/segan_hip.h)
 ADDITIVE_PN0 = 2

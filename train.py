@@ -103,6 +103,11 @@ FLAGS = [
     ('--eval_srmr', dict(action='store_true', default=False,
                          help='the evaluation also reports SRMR (speech-to-reverberation '
                               'modulation energy ratio; needs no clean signal)')),
+    ('--eval_f0', dict(action='store_true', default=False,
+                       help='the evaluation also reports the F0 mean absolute error, the voiced / '
+                            'unvoiced accuracy and the log-F0 KL divergence (f0_mae, vuv_acc, '
+                            'f0_kld) on YIN pitch contours; the validation objective stays '
+                            'SSNR')),
     ('--slice_workers', dict(type=int, default=1)),
     ('--num_workers', dict(type=int, default=1)),
     ('--no-cuda', dict(action='store_true', default=False)),
