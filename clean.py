@@ -12,6 +12,13 @@ leans on librosa.load(path, 16000) or an offline sox pass), and with --keep_rate
 signal is converted back and written at the file's own rate and length.  --srmr prints the SRMR
 (quality.srmr, the speech-to-reverberation modulation energy ratio, which needs no clean signal)
 of each enhanced signal at 16 kHz and the mean over the files.
+
+    python clean.py --baseline logmmse --test_files noisy_dir --synthesis_path out --cuda
+
+--baseline {wiener,logmmse} enhances with a statistical-model baseline (segan_pytorch_amd.baselines)
+instead of a generator: no --cfg_file and no checkpoint, no normalisation and no pre-emphasis; an
+int16 file is written as int16 (rounded, clipped), any other as float32.  --resample, --keep_rate
+and --srmr apply as above.
 """
 import argparse
 import glob
@@ -25,10 +32,13 @@ import numpy as np
 import torch
 from scipy.io import wavfile
 
+from segan_pytorch_amd import baselines
 from segan_pytorch_amd.datasets import normalize_wave_minmax, pre_emphasize
 from segan_pytorch_amd.models import SEGAN, WSEGAN
 from segan_pytorch_amd.ops import RESAMPLE_BETA, RESAMPLE_ZEROS
-from segan_pytorch_amd.resample import TARGET_RATE, resample_wav
+from segan_pytorch_amd.resample import TARGET_RATE, as_mono, resample_wav
+
+BASELINES = ('wiener', 'logmmse')
 
 
 def build_parser():
@@ -58,6 +68,9 @@ def build_parser():
     p.add_argument('--srmr', action='store_true', default=argparse.SUPPRESS,
                    help='print the SRMR (speech-to-reverberation modulation energy ratio) of each '
                         'enhanced signal at 16 kHz, and the mean')
+    p.add_argument('--baseline', choices=BASELINES, default=argparse.SUPPRESS,
+                   help='enhance with this statistical-model baseline instead of a generator; '
+                        'needs neither --cfg_file nor --g_pretrained_ckpt')
     return p
 
 
@@ -70,22 +83,27 @@ def resample_opts(opts):
 
 def main(opts):
     resample, keep_rate, rs_zeros, rs_beta = resample_opts(opts)
-    if opts.cfg_file is None or opts.test_files is None or opts.g_pretrained_ckpt is None:
+    baseline = getattr(opts, 'baseline', None)
+    if baseline is not None:
+        if opts.test_files is None:
+            raise SystemExit('--test_files is required')
+    elif opts.cfg_file is None or opts.test_files is None or opts.g_pretrained_ckpt is None:
         raise SystemExit('--cfg_file, --test_files and --g_pretrained_ckpt are required')
     if not (opts.cuda and torch.cuda.is_available()):
         raise SystemExit('segan_pytorch_amd runs only on an MI355X (HIP) device; pass --cuda on a '
                          'GPU machine (there is no CPU fallback)')
     if opts.h5:
         raise NotImplementedError('--h5 input is not implemented')
-    with open(opts.cfg_file, 'r') as f:
-        cfg = json.load(f)
-    cfg.setdefault('reg_loss', 'l1_loss')      # older train.opts predate this flag
-    args = SimpleNamespace(**cfg)
-    args.cuda = True
-    segan = (WSEGAN if getattr(args, 'wsegan', False) else SEGAN)(args)
-    segan.G.load_pretrained(opts.g_pretrained_ckpt, True)
-    segan.cuda()
-    segan.G.eval()
+    if baseline is None:
+        with open(opts.cfg_file, 'r') as f:
+            cfg = json.load(f)
+        cfg.setdefault('reg_loss', 'l1_loss')      # older train.opts predate this flag
+        args = SimpleNamespace(**cfg)
+        args.cuda = True
+        segan = (WSEGAN if getattr(args, 'wsegan', False) else SEGAN)(args)
+        segan.G.load_pretrained(opts.g_pretrained_ckpt, True)
+        segan.cuda()
+        segan.G.eval()
     if len(opts.test_files) == 1 and os.path.isdir(opts.test_files[0]):
         twavs = sorted(glob.glob(os.path.join(opts.test_files[0], '*.wav')))
     else:
@@ -99,14 +117,19 @@ def main(opts):
         convert = resample and rate != TARGET_RATE
         if convert:
             wav = resample_wav(wav, rate, TARGET_RATE, rs_zeros, rs_beta)
-        wav = pre_emphasize(normalize_wave_minmax(wav), args.preemph)
-        pwav = torch.as_tensor(wav, dtype=torch.float32).view(1, 1, -1).cuda()
-        g_wav, _g_c = segan.generate(pwav, device='cuda')
         out_path = os.path.join(opts.synthesis_path, os.path.basename(twav))
-        g_wav, out_rate = np.asarray(g_wav, dtype=np.float32), int(16e3)
+        if baseline is None:
+            wav = pre_emphasize(normalize_wave_minmax(wav), args.preemph)
+            pwav = torch.as_tensor(wav, dtype=torch.float32).view(1, 1, -1).cuda()
+            g_wav, _g_c = segan.generate(pwav, device='cuda')
+            g_wav, out_rate = np.asarray(g_wav, dtype=np.float32), int(16e3)
+        else:
+            g_wav, out_rate = baselines.denoise_wav(as_mono(wav), baseline), int(16e3)
         if with_srmr:
             from segan_pytorch_amd import quality
-            srmrs.append(float(quality.srmr(torch.from_numpy(g_wav.reshape(-1)).cuda())[0]))
+            f_wav = g_wav / 32768 if g_wav.dtype == np.int16 else g_wav
+            f_wav = np.asarray(f_wav, dtype=np.float32).reshape(-1)
+            srmrs.append(float(quality.srmr(torch.from_numpy(f_wav).cuda())[0]))
         if convert and keep_rate:
             g_wav = resample_wav(g_wav.reshape(-1), TARGET_RATE, rate, rs_zeros, rs_beta)[:n_in]
             out_rate = rate

@@ -3,7 +3,7 @@ the clean wavs of the same names, on the MI355X: the reference's eval_noisy_perf
 
     python eval_noisy_performance.py --test_wavs DIR --clean_wavs DIR --logfile FILE [--stoi]
                                      [--estoi] [--fwsegsnr] [--cd] [--sisdr] [--sdr] [--srmr]
-                                     [--f0] [--resample]
+                                     [--f0] [--resample] [--baseline {wiener,logmmse}]
 
 16 kHz wavs only (int16 files are scaled by 1/32768, float files used as they are), unless
 --resample converts files of other rates to 16 kHz on the GPU first (int16 files to int16, float
@@ -21,7 +21,10 @@ speech-to-reverberation modulation energy ratio of the degraded file alone: it n
 signal) and its mean line.  --f0 adds, after every other column, F0MAE, VUV and F0KLD
 (quality.f0_eval: the F0 mean absolute error in Hz, the voiced / unvoiced accuracy and the KL
 divergence between the log-F0 distributions, on YIN contours tracked on the GPU) and, for each, a
-final mean line over the files where it is finite with the count of NaN files."""
+final mean line over the files where it is finite with the count of NaN files.  --baseline
+{wiener,logmmse} passes every degraded file through that statistical-model enhancer
+(segan_pytorch_amd.baselines, at 16 kHz, float32) before all measures, so that one run gives the
+baseline's row of a results table; the header line and the columns are unchanged."""
 import argparse
 import glob
 import os
@@ -78,8 +81,9 @@ def main(opts):
     if not torch.cuda.is_available():
         raise SystemExit('segan_pytorch_amd runs only on an MI355X (HIP) device; pass --cuda on a '
                          'GPU machine (there is no CPU fallback)')
-    from segan_pytorch_amd import quality
+    from segan_pytorch_amd import baselines, quality
     from segan_pytorch_amd.quality import composite_eval
+    baseline = getattr(opts, 'baseline', None)
     extra = [(name, getattr(quality, fn)) for name, flag, fn in EXTRA if getattr(opts, flag)]
     noisy_wavs = sorted(glob.glob(os.path.join(opts.test_wavs, '*.wav')))
     metrics = {'csig': [], 'cbak': [], 'covl': [], 'STOI': [], 'ESTOI': [], 'FWSEGSNR': [],
@@ -94,6 +98,9 @@ def main(opts):
             clean_wav = os.path.join(opts.clean_wavs, bname + '.wav')
             noisy = read_wav(noisy_wav, opts)
             clean = read_wav(clean_wav, opts)
+            if baseline is not None:
+                noisy = baselines.denoise(torch.from_numpy(noisy).cuda(),
+                                          rule=baseline).cpu().numpy()
             beg_t = timeit.default_timer()
             r = composite_eval(torch.from_numpy(clean).cuda(), torch.from_numpy(noisy).cuda())
             csig, cbak, covl, pesq, ssnr = (float(r[k][0]) for k in
@@ -166,6 +173,9 @@ def build_parser():
                         help='also compute F0MAE, VUV and F0KLD (F0 mean absolute error in Hz, '
                              'voiced / unvoiced accuracy, KL divergence of the log-F0 '
                              'distributions) on YIN pitch contours')
+    parser.add_argument('--baseline', choices=('wiener', 'logmmse'), default=None,
+                        help='enhance every degraded file with this statistical-model baseline '
+                             'before all measures')
     parser.add_argument('--resample', action='store_true', default=False,
                         help='convert wavs that are not 16 kHz to 16 kHz on the GPU instead of '
                              'refusing them')

@@ -589,6 +589,45 @@ int segan_f0_eval(const double* f0_ref, const int* lag_ref, const double* f0_deg
                   const int* lag_deg, const int* nframes, int rows, int F, double* out4,
                   void* stream);
 
+/* ---- Wiener and log-MMSE baseline enhancers ----------------------------
+ * One short-time spectral enhancer with two gain rules, defined by scripts/denoise_oracle.py: the
+ * decision-directed a-priori SNR of Ephraim & Malah with the VAD-gated noise estimate of Loizou's
+ * wiener_as / logmmse programs, written from the literature.  Rows x [rows][T] of x_dtype
+ * (SEGAN_DT_F32 or SEGAN_DT_F64) at srate 16000 or 8000, row r restricted to its first lengths[r]
+ * samples L (device int[rows], clamped to 0 .. T; NULL: all T); all arithmetic fp64.  F = srate /
+ * 50, H = F / 2, N = 2 F; w = the Hamming window 0.54 - 0.46 cos(2 pi n / (F - 1)) times H / sum w.
+ *   lambda[k] = max(m[k]^2, 2^-100), m = the mean of |DFT_N(w x[j F : (j + 1) F])[k]| over j < 6
+ *     added in ascending j, k = 0 .. F;
+ *   frame t < nf = L / H - 1: S = DFT_N(w x[t H : t H + F]), s2 = |S|^2, gamma = min(s2 / lambda,
+ *     40), xi = max(0.98 P / lambda + (1 - 0.98) max(gamma - 1, 0), 10^-2.5), P = |G S|^2 of the
+ *     frame before (t = 0: the first term is 0.98);
+ *   v_t = (sum_k c_k (gamma xi / (1 + xi) - log(1 + xi))) / F, c = 1, 2, .., 2, 1, the bins added
+ *     in groups of 64 (ascending k inside a group from zero, then the groups in ascending order
+ *     from zero); v_t < 0.15: lambda <- max(0.98 lambda + 0.02 s2, 2^-100) after gamma and xi of
+ *     the frame were formed;
+ *   A = xi / (1 + xi); G = A (SEGAN_DENOISE_WIENER, Scalart & Filho 1996) or A exp(E1(max(A gamma,
+ *     2^-40)) / 2) (SEGAN_DENOISE_LOGMMSE, Ephraim & Malah 1985; not clipped), E1 by its power
+ *     series below 1 and the modified Lentz continued fraction from 1 on, to a relative step 2^-53;
+ *   y[n] = sum_t o_t[n - t H], o_t = the first F samples of real(IDFT_N(G S)) with the Hermitian
+ *     extension, the earlier frame added first; y[n] = 0 from (nf + 1) H to T.
+ *   L < 6 F: nf = 0 and y = x below L, 0 from L on.
+ *   segan_denoise_dims (host only): out[5] = {F, H, N, nf of a row of T samples, the bytes of
+ *     workspace `ws` for `rows` rows: 16 (F + 1) nf + 8 (F + 1) a row}.
+ *   segan_denoise: y [rows][T] of y_dtype (SEGAN_DT_F64, or SEGAN_DT_F32 rounded once), nframes
+ *     int[rows]; vad double[rows][nf of T] = v_t and update int[rows][nf of T] = 1 where lambda was
+ *     updated at the frame, each optional (NULL), NaN and -1 from the row's own nf on.  ws: 16-byte
+ *     aligned.
+ * No atomics, no scratch, every sum in an order fixed by the indices: a row's bits depend neither
+ * on T, nor on the other rows, nor on the samples past its length.  rows in 1 .. 65535, T in
+ * 1 .. 2^24, checked before any launch.  Added without a change of SEGAN_ABI_VERSION: the exports
+ * are purely additive. */
+#define SEGAN_DENOISE_WIENER 0
+#define SEGAN_DENOISE_LOGMMSE 1
+int segan_denoise_dims(int rows, int T, int srate, long long* out);
+int segan_denoise(const void* x, int x_dtype, const int* lengths, int rows, int T, int srate,
+                  int rule, void* y, int y_dtype, int* nframes, double* vad, int* update, void* ws,
+                  void* stream);
+
 /* ---- on-the-fly additive noise (the reference's Additive, utils.py:43-297)
  * fp64 arithmetic on fp32 rows x / clean [rows][T], row r restricted to its first lengths[r]
  * samples (device int[rows], clamped to 0 .. T; NULL: all T).  One workgroup per row, no atomics:

@@ -114,6 +114,8 @@ SIGNATURES = {
     'segan_pitch': (c_int, [_P, _P, c_int, c_int, c_int, c_double, _P, _P, _P, _P, _P]),
     'segan_pitch_cmnd': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P]),
     'segan_f0_eval': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, _P]),
+    'segan_denoise_dims': (c_int, [c_int, c_int, c_int, POINTER(c_int64)]),
+    'segan_denoise': (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P, _P]),
     'segan_asl_p56': (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     'segan_additive_mix': (c_int, [_P, _P, _P, c_int64, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P]),
     'segan_resample_plan': (c_int, [c_int, c_int, c_int, c_double, POINTER(c_int), POINTER(c_int), _P, c_int]),

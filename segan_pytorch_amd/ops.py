@@ -1554,6 +1554,103 @@ def f0_eval(f0_ref, lag_ref, f0_deg, lag_deg, nframes=None):
     return out
 
 
+DENOISE_RULES = {'wiener': 0, 'logmmse': 1}      # SEGAN_DENOISE_* (include/segan_hip.h)
+DENOISE_RATES = (8000, 16000)
+DENOISE_MAX_T = 1 << 24
+DENOISE_WS_CAP = 1 << 30     # bytes of workspace one call of segan_denoise may take
+_DENOISE_DT = {torch.float32: 0, torch.float64: 2}       # SEGAN_DT_*
+
+
+def denoise_dims(rows, T, srate=16000):
+    """segan_denoise_dims (host only) as a dict: frame, hop and nfft at `srate`, the frames of a
+    row of T samples, ws_bytes for `rows` rows."""
+    dims = (ctypes.c_int64 * 5)()
+    check(_lib.load().segan_denoise_dims(rows, T, srate, dims), 'denoise')
+    return dict(zip(('frame', 'hop', 'nfft', 'frames', 'ws_bytes'), list(dims)))
+
+
+def _denoise_run(x, lengths, srate, rule, out_dtype, ws_cap, stages):
+    if not isinstance(x, torch.Tensor):
+        raise TypeError('x must be a tensor, got {}'.format(type(x)))
+    if x.dtype not in _DENOISE_DT:
+        raise TypeError('x must be float32 or float64, got {}'.format(x.dtype))
+    _chk(x, 'x', None, x.dtype)
+    if x.dim() not in (1, 2):
+        raise ValueError('denoise: x must be [rows, T] or [T], got {}'.format(tuple(x.shape)))
+    x2 = x.reshape(-1, x.shape[-1])
+    rows, T = x2.shape
+    if not 1 <= rows <= 65535 or not 1 <= T <= DENOISE_MAX_T:
+        raise ValueError('denoise: 1 .. 65535 rows of 1 .. 2^24 samples, got {}'.format(
+            tuple(x.shape)))
+    if isinstance(srate, bool) or srate not in DENOISE_RATES:
+        raise ValueError('denoise: srate must be one of {}, got {!r}'.format(DENOISE_RATES, srate))
+    if not isinstance(rule, str) or rule not in DENOISE_RULES:
+        raise ValueError('denoise: rule must be one of {}, got {!r}'.format(
+            sorted(DENOISE_RULES), rule))
+    out_dtype = x.dtype if out_dtype is None else out_dtype
+    if out_dtype not in _DENOISE_DT:
+        raise ValueError('denoise: out_dtype must be torch.float32 or torch.float64, got '
+                         '{!r}'.format(out_dtype))
+    lens = None if lengths is None else _row_lengths('denoise', lengths, rows, T, x.device)
+    cap = _int_arg(ws_cap, 'denoise: ws_cap', 1, 1 << 62)
+    lib = _lib.load()
+    d = denoise_dims(1, T, srate)
+    per = int(cap // d['ws_bytes'])
+    if per < 1:
+        raise ValueError('denoise: ws_cap of {} bytes is below the {} bytes one row of {} samples '
+                         'needs'.format(cap, d['ws_bytes'], T))
+    per = min(per, rows)
+    ws = _stream_scratch(d['ws_bytes'] * per + 16, x.device)
+    ws = ws[(-ws.data_ptr()) % 16:]
+    nfmax = d['frames']
+    y = torch.empty((rows, T), device=x.device, dtype=out_dtype)
+    nframes = torch.empty(rows, device=x.device, dtype=torch.int32)
+    vad = upd = None
+    if stages:
+        vad = torch.empty((rows, max(nfmax, 1)), device=x.device, dtype=torch.float64)
+        upd = torch.empty((rows, max(nfmax, 1)), device=x.device, dtype=torch.int32)
+    for r0 in range(0, rows, per):
+        n = min(per, rows - r0)
+        check(lib.segan_denoise(_ptr(x2[r0:r0 + n]), _DENOISE_DT[x.dtype],
+                                _ptr(None if lens is None else lens[r0:r0 + n]), n, T, srate,
+                                DENOISE_RULES[rule], _ptr(y[r0:r0 + n]), _DENOISE_DT[out_dtype],
+                                _ptr(nframes[r0:r0 + n]),
+                                _ptr(None if vad is None else vad[r0:r0 + n]),
+                                _ptr(None if upd is None else upd[r0:r0 + n]), _ptr(ws),
+                                _stream()), 'denoise')
+    out = {'y': y.reshape(x.shape), 'nframes': nframes}
+    if stages:
+        out['vad'], out['noise_update'] = vad[:, :nfmax], upd[:, :nfmax]
+    return out
+
+
+def denoise_stages(x, lengths=None, srate=16000, rule='logmmse', out_dtype=None,
+                   ws_cap=DENOISE_WS_CAP):
+    """`denoise_rows` with what its decisions rest on, as a dict of device
+    tensors: 'y' (shaped like x), 'nframes' [rows] (int32: each row's own frame count, 0 for a row
+    returned unchanged), 'vad' [rows, nf of T] (fp64: v_t, the mean log likelihood ratio of the
+    frame; NaN from the row's own count on) and 'noise_update' [rows, nf of T] (int32: 1 where
+    v_t < 0.15 and the noise estimate took the frame in, else 0; -1 from the row's own count
+    on)."""
+    return _denoise_run(x, lengths, srate, rule, out_dtype, ws_cap, True)
+
+
+def denoise_rows(x, lengths=None, srate=16000, rule='logmmse', out_dtype=None,
+                 ws_cap=DENOISE_WS_CAP):
+    """The Wiener (`rule='wiener'`, Scalart & Filho 1996) or log-MMSE (`rule='logmmse'`, Ephraim &
+    Malah 1985) enhancement of each row of x ([rows, T] or [T], fp32 or fp64 CUDA tensor) at
+    `srate` (16000 or 8000) on the device, all arithmetic fp64: 20 ms Hamming frames at half
+    overlap, a 40 ms DFT, the decision-directed a-priori SNR (0.98), the noise spectrum taken
+    from the first 120 ms and updated in the frames a likelihood-ratio VAD calls noise.  The
+    definition is scripts/denoise_oracle.py.  Row r is x[r, :lengths[r]] (host integers 0 .. T;
+    all T without `lengths`); a row shorter than 120 ms is returned unchanged; the output is zero
+    from (nframes + 1) hops on, and of `out_dtype` (torch.float32, rounded once, or
+    torch.float64; x's own by default).  The rows are processed in chunks whose workspace stays
+    under `ws_cap` bytes.  Fixed operation order: a batched row equals its own call bit for bit,
+    whatever the chunking."""
+    return _denoise_run(x, lengths, srate, rule, out_dtype, ws_cap, False)['y']
+
+
 ASL_THRESHOLDS = 15      # nbits - 1 thresholds 2^-15 .. 2^-1 (nbits = 16)
 ADDITIVE_CAP = 1         # status bits of asl_p56 / additive_mix (include/segan_hip.h)
 ADDITIVE_PN0 = 2
