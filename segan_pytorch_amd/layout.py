@@ -28,9 +28,9 @@ Nothing in here runs on the product path: the product packs weights on the GPU.
 """
 import numpy as np
 
+from ._lib import PAD_REFLECT, PAD_ZERO      # noqa: F401  (the header's SEGAN_PAD_*)
+
 KP = 32          # taps are padded to 32 so every phase has U = 32 // S taps
-PAD_REFLECT = 0
-PAD_ZERO = 1
 
 
 def taps_per_phase(S):

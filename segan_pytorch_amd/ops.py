@@ -18,7 +18,8 @@ from ._lib import ACT_NONE, ACT_TANH, PAD_REFLECT, PAD_ZERO, SeganSrc, check
 
 import os as _os
 
-PREC_FP32, PREC_BF16, PREC_BF16X3 = 0, 1, 3
+_D = _lib.DEFINES       # the integer macros of include/segan_hip.h
+PREC_FP32, PREC_BF16, PREC_BF16X3 = _D['SEGAN_PREC_FP32'], _D['SEGAN_PREC_BF16'], _D['SEGAN_PREC_BF16X3']
 _PREC_NAMES = {'fp32': PREC_FP32, 'bf16': PREC_BF16, 'bf16x3': PREC_BF16X3}
 _precision = _PREC_NAMES[_os.environ.get('SEGAN_PRECISION', 'fp32')]
 _EUNSUPPORTED = -3
@@ -49,7 +50,7 @@ _ACC_NAMES = ('plain', 'blocked')
 _accumulation = _os.environ.get('SEGAN_ACCUMULATION', 'plain')
 if _accumulation not in _ACC_NAMES:
     raise ValueError('SEGAN_ACCUMULATION must be one of {}'.format(_ACC_NAMES))
-PREC_FP32_BLOCKED = 4
+PREC_FP32_BLOCKED = _D['SEGAN_PREC_FP32_BLOCKED']
 
 
 def set_accumulation(mode):
@@ -108,7 +109,7 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
-def _chk(t, name, ndim=None, dtype=torch.float32):
+def _chk(t, name, ndim=None, dtype=torch.float32, contiguous=True):
     if not isinstance(t, torch.Tensor):
         raise TypeError('{} must be a tensor, got {}'.format(name, type(t)))
     if not t.is_cuda:
@@ -117,11 +118,20 @@ def _chk(t, name, ndim=None, dtype=torch.float32):
             'there is no CPU path'.format(name, t.device))
     if t.dtype != dtype:
         raise TypeError('{} must be {}, got {}'.format(name, str(dtype)[len('torch.'):], t.dtype))
-    if not t.is_contiguous():
+    if contiguous and not t.is_contiguous():
         raise ValueError('{} must be contiguous'.format(name))
     if ndim is not None and t.dim() != ndim:
         raise ValueError('{} must have {} dims, got {}'.format(name, ndim, tuple(t.shape)))
     return t
+
+
+def _chk_pair(what, ref, deg):
+    """ref and deg are fp32 CUDA [rows, T] of one shape; returns (rows, T)."""
+    _chk(ref, 'ref', 2)
+    _chk(deg, 'deg', 2)
+    if ref.shape != deg.shape:
+        raise ValueError('{}: shapes differ {} vs {}'.format(what, tuple(ref.shape), tuple(deg.shape)))
+    return ref.shape
 
 
 class Src(object):
@@ -1035,11 +1045,7 @@ def de_emphasize(y, coef):
 def ssnr(ref, deg, srate=16000, eps=1e-10):
     """Segmental SNR of utils.py:350-395 per row of ref / deg [rows, T] on the device.  Returns
     (overall_snr[rows], mean_segmental_snr[rows], segmental[rows, nframes])."""
-    _chk(ref, 'ref', 2)
-    _chk(deg, 'deg', 2)
-    if ref.shape != deg.shape:
-        raise ValueError('ssnr: shapes differ {} vs {}'.format(tuple(ref.shape), tuple(deg.shape)))
-    rows, T = ref.shape
+    rows, T = _chk_pair('ssnr', ref, deg)
     lib = _lib.load()
     nf = lib.segan_ssnr_frames(T, srate)
     seg = torch.empty((rows, max(nf, 1)), device=ref.device, dtype=torch.float32)
@@ -1050,11 +1056,7 @@ def ssnr(ref, deg, srate=16000, eps=1e-10):
 
 
 def _quality_frames(fn, what, ref, deg, srate):
-    _chk(ref, 'ref', 2)
-    _chk(deg, 'deg', 2)
-    if ref.shape != deg.shape:
-        raise ValueError('{}: shapes differ {} vs {}'.format(what, tuple(ref.shape), tuple(deg.shape)))
-    rows, T = ref.shape
+    rows, T = _chk_pair(what, ref, deg)
     nf = _lib.load().segan_ssnr_frames(T, srate)
     dist = torch.empty((rows, max(nf, 1)), device=ref.device, dtype=torch.float64)
     check(fn(_ptr(ref), _ptr(deg), _ptr(dist), rows, T, srate, _stream()), what)
@@ -1128,12 +1130,8 @@ def _row_lengths(what, lengths, rows, T, device, device_ok=False):
 def _stoi_run(entry, last, per, ref, deg, srate, lengths):
     """The argument checks, stage buffers and call that segan_stoi and segan_estoi share: `entry`
     names the C entry, `last` its last-stage buffer ([rows, S, per], [rows, S] with per = 1)."""
-    _chk(ref, 'ref', 2)
-    _chk(deg, 'deg', 2)
-    if ref.shape != deg.shape:
-        raise ValueError('stoi: shapes differ {} vs {}'.format(tuple(ref.shape), tuple(deg.shape)))
+    rows, T = _chk_pair('stoi', ref, deg)
     srate = _int_arg(srate, 'stoi: srate', *STOI_SRATES)
-    rows, T = ref.shape
     lens = None if lengths is None else _row_lengths('stoi', lengths, rows, T, ref.device)
     lib = _lib.load()
     dims = (ctypes.c_int * 5)()
@@ -1196,18 +1194,14 @@ def estoi(ref, deg, srate=16000, lengths=None):
     return estoi_stages(ref, deg, srate, lengths)['d']
 
 
-SISDR_SPAN = 4096        # SEGAN_SISDR_SPAN (include/segan_hip.h): samples per partial sum
+SISDR_SPAN = _D['SEGAN_SISDR_SPAN']      # samples per partial sum
 
 
 def _measure_args(what, ref, deg, lengths):
     """The argument checks of ops.stoi for the measures with per-row lengths: fp32 CUDA [rows, T]
     of one shape, host integers 1 <= lengths[r] <= T.  Returns (rows, T, device int32 lengths or
     None)."""
-    _chk(ref, 'ref', 2)
-    _chk(deg, 'deg', 2)
-    if ref.shape != deg.shape:
-        raise ValueError('{}: shapes differ {} vs {}'.format(what, tuple(ref.shape), tuple(deg.shape)))
-    rows, T = ref.shape
+    rows, T = _chk_pair(what, ref, deg)
     if rows < 1 or T < 1:
         raise ValueError('{}: empty input {}'.format(what, tuple(ref.shape)))
     lens = None
@@ -1270,8 +1264,8 @@ def si_sdr(ref, deg, lengths=None):
     return out
 
 
-SDR_TAPS = 512           # SEGAN_SDR_MAX_TAPS (include/segan_hip.h): the longest distortion filter
-SDR_SPAN = 4096          # SEGAN_SDR_SPAN: samples per partial sum
+SDR_TAPS = _D['SEGAN_SDR_MAX_TAPS']      # the longest distortion filter
+SDR_SPAN = _D['SEGAN_SDR_SPAN']          # samples per partial sum
 
 
 def sdr_stages(ref, deg, lengths=None, taps=SDR_TAPS):
@@ -1281,11 +1275,7 @@ def sdr_stages(ref, deg, lengths=None, taps=SDR_TAPS):
     the order reached on), 'order' [rows] (int64: taps unless the recursion's guard stopped it),
     'target_energy', 'error_energy', 'sdr' [rows].  Row r is ref[r, :lengths[r]] (host integers
     0 .. T; all T without `lengths`).  No device-to-host copy."""
-    _chk(ref, 'ref', 2)
-    _chk(deg, 'deg', 2)
-    if ref.shape != deg.shape:
-        raise ValueError('sdr: shapes differ {} vs {}'.format(tuple(ref.shape), tuple(deg.shape)))
-    rows, T = ref.shape
+    rows, T = _chk_pair('sdr', ref, deg)
     if not 1 <= rows <= 65535 or T < 1:
         raise ValueError('sdr: 1 .. 65535 rows of at least one sample, got {}'.format(
             tuple(ref.shape)))
@@ -1320,14 +1310,8 @@ def toeplitz_solve(r, d):
     recursion on the device.  Returns (c fp64 like r, order int32 [rows]): at order m with
     prediction error E_m <= 2^-40 r[0] the recursion stops, c[m:] is zero and order is m; else
     order is n."""
-    for t, name in ((r, 'r'), (d, 'd')):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError('{} must be a tensor, got {}'.format(name, type(t)))
-        if not t.is_cuda:
-            raise RuntimeError('{} is on {}: segan_pytorch_amd runs only on an MI355X (HIP) device; '
-                               'there is no CPU path'.format(name, t.device))
-        if t.dtype != torch.float64:
-            raise TypeError('{} must be float64, got {}'.format(name, t.dtype))
+    _chk(r, 'r', dtype=torch.float64, contiguous=False)
+    _chk(d, 'd', dtype=torch.float64, contiguous=False)
     if r.shape != d.shape or r.dim() not in (1, 2):
         raise ValueError('toeplitz_solve: r {} and d {} must be [rows, n] or [n] of one shape'
                          .format(tuple(r.shape), tuple(d.shape)))
@@ -1343,11 +1327,11 @@ def toeplitz_solve(r, d):
     return c.reshape(r.shape), order
 
 
-FFT_MAX_LOG2 = 20        # SEGAN_FFT_MAX_LOG2 (include/segan_hip.h): the longest transform, 2^20
-FFT_LDS_LOG2 = 12        # SEGAN_FFT_LDS_LOG2: up to 2^12 points one workgroup transforms in LDS
-SRMR_CHANNELS = 23       # SEGAN_SRMR_CHANNELS: gammatone channels
-SRMR_BANDS = 8           # SEGAN_SRMR_BANDS: modulation bands
-SRMR_STAGE = 234         # SEGAN_SRMR_STAGE: doubles of one row's stage block
+FFT_MAX_LOG2 = _D['SEGAN_FFT_MAX_LOG2']      # the longest transform, 2^20
+FFT_LDS_LOG2 = _D['SEGAN_FFT_LDS_LOG2']      # up to 2^12 points one workgroup transforms in LDS
+SRMR_CHANNELS = _D['SEGAN_SRMR_CHANNELS']    # gammatone channels
+SRMR_BANDS = _D['SEGAN_SRMR_BANDS']          # modulation bands
+SRMR_STAGE = _D['SEGAN_SRMR_STAGE']          # doubles of one row's stage block
 SRMR_RATES = (8000, 16000)
 SRMR_WS_CAP = 1 << 30    # bytes of workspace one call of segan_srmr may take
 
@@ -1357,13 +1341,7 @@ def fft_pow2(x, inverse=False):
     n a power of two from 2 to 2^20) on the device, numpy.fft.fft's sign and scaling
     (`inverse=True`: numpy.fft.ifft's, with 1/n).  Up to n = 4096 one workgroup transforms a row
     in LDS; above that the transform runs as two levels.  Returns a new tensor like x."""
-    if not isinstance(x, torch.Tensor):
-        raise TypeError('x must be a tensor, got {}'.format(type(x)))
-    if not x.is_cuda:
-        raise RuntimeError('x is on {}: segan_pytorch_amd runs only on an MI355X (HIP) device; '
-                           'there is no CPU path'.format(x.device))
-    if x.dtype != torch.complex128:
-        raise TypeError('x must be complex128, got {}'.format(x.dtype))
+    _chk(x, 'x', dtype=torch.complex128, contiguous=False)
     if x.dim() not in (1, 2):
         raise ValueError('fft_pow2: x must be [rows, n] or [n], got {}'.format(tuple(x.shape)))
     x2 = x.reshape(-1, x.shape[-1]).contiguous()
@@ -1436,7 +1414,7 @@ def srmr(x, lengths=None, rate=16000, ws_cap=SRMR_WS_CAP):
     return srmr_stages(x, lengths, rate, ws_cap)['srmr']
 
 
-PITCH_NB = 5             # SEGAN_PITCH_NB: hop blocks per frame
+PITCH_NB = _D['SEGAN_PITCH_NB']      # hop blocks per frame
 PITCH_RATES = (8000, 16000)
 PITCH_THETA = 0.15       # YIN's threshold on the normalised difference
 PITCH_MAX_T = 1 << 24
@@ -1554,11 +1532,11 @@ def f0_eval(f0_ref, lag_ref, f0_deg, lag_deg, nframes=None):
     return out
 
 
-DENOISE_RULES = {'wiener': 0, 'logmmse': 1}      # SEGAN_DENOISE_* (include/segan_hip.h)
+DENOISE_RULES = {'wiener': _D['SEGAN_DENOISE_WIENER'], 'logmmse': _D['SEGAN_DENOISE_LOGMMSE']}
 DENOISE_RATES = (8000, 16000)
 DENOISE_MAX_T = 1 << 24
 DENOISE_WS_CAP = 1 << 30     # bytes of workspace one call of segan_denoise may take
-_DENOISE_DT = {torch.float32: 0, torch.float64: 2}       # SEGAN_DT_*
+_DENOISE_DT = {torch.float32: _D['SEGAN_DT_F32'], torch.float64: _D['SEGAN_DT_F64']}
 
 
 def denoise_dims(rows, T, srate=16000):
@@ -1813,7 +1791,7 @@ RESAMPLE_ZEROS = 32          # the one default of every layer: flat to 7.5 kHz a
 RESAMPLE_BETA = 8.6          # beyond 9 kHz for 48 -> 16 kHz.  (10, 5.0) is scipy's default.
 RESAMPLE_ZEROS_MAX = 64
 RESAMPLE_BETA_MAX = 20.0
-_RESAMPLE_DT = {torch.float32: 0, torch.int16: 1, torch.float64: 2}    # SEGAN_DT_*
+_RESAMPLE_DT = {torch.float32: _D['SEGAN_DT_F32'], torch.int16: _D['SEGAN_DT_I16'], torch.float64: _D['SEGAN_DT_F64']}
 
 
 def _resample_args(rate_in, rate_out, zeros, beta):
@@ -1952,9 +1930,9 @@ def preemph_rows(x, prev, first, out, coef, index=None):
 # ---------------------------------------------------------------------------------
 # reverberation
 # ---------------------------------------------------------------------------------
-REVERB_P = 128           # SEGAN_REVERB_P (include/segan_hip.h): the partition; transforms are 2P
-REVERB_RIR = 1           # status bits of reverb_rows (SEGAN_REVERB_ST_*)
-REVERB_DELAY = 2
+REVERB_P = _D['SEGAN_REVERB_P']              # the partition; transforms are 2P
+REVERB_RIR = _D['SEGAN_REVERB_ST_RIR']       # status bits of reverb_rows
+REVERB_DELAY = _D['SEGAN_REVERB_ST_DELAY']
 _reverb_bases = {}
 _reverb_ws = {}
 
@@ -2114,13 +2092,13 @@ def reverb_stages(x, bank, rir_ids, lengths=None, prev=None, X=None, yt=None):
 # clipping, chunk removal and band limiting
 # ---------------------------------------------------------------------------------
 DISTORT_MAX_ROWS = 65535
-CLIP_SILENT = 1          # status bits of clip_rows (SEGAN_CLIP_ST_*)
-CLIP_FACTOR = 2
-CHOP_MAX = 8             # SEGAN_CHOP_MAX: chunks per row
-CHOP_NOLEVEL = 1         # status bit of chop_rows
-FIR_MAX_K = 2048         # SEGAN_FIR_MAX_K: the longest one-sided filter
-FIR_TILE = 1024          # SEGAN_FIR_TILE: outputs per workgroup
-FIR_ID = 1               # status bit of fir_rows
+CLIP_SILENT = _D['SEGAN_CLIP_ST_SILENT']     # status bits of clip_rows
+CLIP_FACTOR = _D['SEGAN_CLIP_ST_FACTOR']
+CHOP_MAX = _D['SEGAN_CHOP_MAX']              # chunks per row
+CHOP_NOLEVEL = _D['SEGAN_CHOP_ST_NOLEVEL']   # status bit of chop_rows
+FIR_MAX_K = _D['SEGAN_FIR_MAX_K']            # the longest one-sided filter
+FIR_TILE = _D['SEGAN_FIR_TILE']              # outputs per workgroup
+FIR_ID = _D['SEGAN_FIR_ST_ID']               # status bit of fir_rows
 
 
 def _distort_rows(what, x, lengths, prev):
@@ -2255,13 +2233,13 @@ def fir_rows(x, bank, K, ids, lengths=None, prev=None, out_dtype=None):
 # ---------------------------------------------------------------------------------
 # whispered speech: noise-excited LPC resynthesis
 # ---------------------------------------------------------------------------------
-WHISPER_N = 512          # SEGAN_WHISPER_N: frame
-WHISPER_H = 256          # SEGAN_WHISPER_H: hop
-WHISPER_P = 16           # SEGAN_WHISPER_P: order
-WHISPER_WU = 256         # SEGAN_WHISPER_WU: warm-up samples of the synthesis filter
+WHISPER_N = _D['SEGAN_WHISPER_N']            # frame
+WHISPER_H = _D['SEGAN_WHISPER_H']            # hop
+WHISPER_P = _D['SEGAN_WHISPER_P']            # order
+WHISPER_WU = _D['SEGAN_WHISPER_WU']          # warm-up samples of the synthesis filter
 WHISPER_SRATE = 16000
-WHISPER_SILENT = 1       # status bits of whisper_rows (SEGAN_WHISPER_ST_*)
-WHISPER_TILT = 2
+WHISPER_SILENT = _D['SEGAN_WHISPER_ST_SILENT']   # status bits of whisper_rows
+WHISPER_TILT = _D['SEGAN_WHISPER_ST_TILT']
 _whisper_tables_cache = {}
 _whisper_ws = {}
 

@@ -13,6 +13,7 @@ import pytest
 import torch
 from scipy.io import wavfile
 
+import abi_header as H
 from conftest import load_golden
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -236,16 +237,12 @@ def test_loader_checks_the_probability():
 
 def test_header_lib_and_abi_agree():
     from segan_pytorch_amd import _lib
-    hdr = open(os.path.join(ROOT, 'include', 'segan_hip.h')).read()
-    assert re.search(r'#define SEGAN_ABI_VERSION 17\b', hdr)
+    assert H.macro('SEGAN_ABI_VERSION') == 17
     assert _lib.ABI_VERSION == 17
     lib = _lib.load()
     assert lib.segan_abi_version() == 17
-    code = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
     for name in ('segan_asl_p56', 'segan_additive_mix', 'segan_pcm16_wave', 'segan_preemph_rows'):
-        m = re.search(r'\bint ' + name + r'\s*\(([^)]*)\)', code)
-        assert m, name
-        assert len(m.group(1).split(',')) == len(_lib.SIGNATURES[name][1]), name
+        assert len(H.args(name)) == len(_lib.SIGNATURES[name][1]), name
         assert hasattr(lib, name)
     assert 'segan_asl_p56' in open(os.path.join(ROOT, 'INTEGRATION.md')).read()
     # arguments are validated before any launch

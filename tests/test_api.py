@@ -11,14 +11,14 @@ from types import SimpleNamespace
 import pytest
 import torch
 
+import abi_header as H
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_library_exports_every_declared_symbol():
     from segan_pytorch_amd import _lib
-    hdr = open(os.path.join(ROOT, 'include', 'segan_hip.h')).read()
-    hdr = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
-    declared = set(re.findall(r'\b(segan_[a-z0-9_]+)\s*\(', hdr))
+    declared = set(re.findall(r'\b(segan_[a-z0-9_]+)\s*\(', H.CODE))
     declared -= {'segan_src'}
     assert len(declared) >= 25
     lib = _lib.load()
@@ -31,6 +31,60 @@ def test_library_exports_every_declared_symbol():
     assert lib.segan_packed_f_bytes(64, 64, 3) == 0
     rc = lib.segan_fill(None, 0.0, 10, None)
     assert rc != 0 and b'fill' in lib.segan_last_error()
+
+
+def test_binding_is_read_from_the_header():
+    """_lib derives SIGNATURES from the declarations: the same set an independent regex finds, and
+    full types (not just counts) for entries that exercise each mapping, written out here."""
+    from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_void_p
+    from segan_pytorch_amd import _lib
+    P, SRC = c_void_p, POINTER(_lib.SeganSrc)
+    declared = set(re.findall(r'\b(segan_[a-z0-9_]+)\s*\(', H.CODE)) - {'segan_src'}
+    assert set(_lib.SIGNATURES) == declared and len(_lib.SIGNATURES) == 119      # ABI 17
+    pins = {
+        'segan_gemm': (c_int, [P, c_int64, c_int64, P, c_int64, c_int64, P, c_int64, c_int, c_int,
+                               c_int, c_int, c_int, P, c_size_t, P]),
+        'segan_adam_step': (c_int, [P, P, P, P, c_float, c_double, c_double, c_float, c_int, c_int64,
+                                    P]),
+        'segan_allreduce': (c_int, [P, P, c_size_t, c_float, P]),
+        'segan_last_error': (c_char_p, []),
+        'segan_debug_last_corr': (None, [P]),
+        'segan_whisper_ws_doubles': (c_int64, [c_int, c_int]),
+        'segan_conv1d_fwd': (c_int, [SRC, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                     c_int, c_int, c_int, P, c_size_t, P]),
+    }
+    for name, want in pins.items():
+        assert _lib.SIGNATURES[name] == want, name
+    assert list(_lib.SIGNATURES)[:3] == ['segan_abi_version', 'segan_last_error',
+                                         'segan_set_reserved_slots']              # header order
+
+
+def test_header_reader_refuses_what_it_cannot_map():
+    from segan_pytorch_amd._lib import read_header
+    ok = 'int segan_a(const float* x, long long n, void* stream);\n'
+    assert list(read_header(ok)[0]) == ['segan_a']
+    for bad in ('int segan_x(__fp16 a);',                       # a type without a mapping
+                'int segan_x(int a,\n            (int b);',     # a stray parenthesis
+                'int segan_x(int);', 'struct segan_s* segan_x(void);', 'int segan_x(int a[4]);'):
+        with pytest.raises(RuntimeError) as e:
+            read_header(ok + bad + '\n' + ok.replace('segan_a', 'segan_b'))
+        assert ' '.join(bad.split()) in str(e.value), bad
+
+
+def test_header_macros_are_integers_or_absent():
+    from segan_pytorch_amd import _lib
+    D = _lib.DEFINES
+    assert D['SEGAN_ABI_VERSION'] == 17 == H.macro('SEGAN_ABI_VERSION')
+    assert D['SEGAN_REVERB_P'] == 128           # the #ifndef-guarded default
+    assert 'SEGAN_HIP_H' not in D               # the include guard has no value
+    assert all(type(v) is int and k.startswith('SEGAN_') for k, v in D.items())
+    d = _lib.read_header('#define SEGAN_A (1 << 3)\n#define SEGAN_B 0x10  /* hex */\n'
+                         '#ifdef X\n#define SEGAN_C 1\n#else\n#define SEGAN_C 2\n#endif\n'
+                         '#define SEGAN_D 7u\n#define SEGAN_E -3 // signed\n')[1]
+    assert dict(d) == {'SEGAN_B': 16, 'SEGAN_E': -3}
+    for name in ('SEGAN_A', 'SEGAN_C', 'SEGAN_D', 'SEGAN_NOT_THERE'):
+        with pytest.raises(RuntimeError, match=name):
+            d[name]
 
 
 def test_constructor_signatures_match_the_reference():
@@ -303,8 +357,7 @@ def test_reserved_slots_setter_round_trips():
         assert ops.set_reserved_slots(0) == 512
     finally:
         ops.set_reserved_slots(first)
-    hdr = open(os.path.join(ROOT, 'include', 'segan_hip.h')).read()
-    assert 'int segan_set_reserved_slots(int n);' in hdr
+    assert 'int segan_set_reserved_slots(int n);' in H.RAW
 
 
 def test_accumulation_mode_switch():
@@ -320,8 +373,7 @@ def test_accumulation_mode_switch():
         assert ops.get_accumulation() == 'blocked'
     finally:
         ops.set_accumulation('plain')
-    hdr = open(os.path.join(ROOT, 'include', 'segan_hip.h')).read()
-    assert '#define SEGAN_PREC_FP32_BLOCKED 4' in hdr
+    assert H.macro('SEGAN_PREC_FP32_BLOCKED') == 4
 
 
 def test_purge_checkpoints_keeps_the_newest(tmp_path):

@@ -2,13 +2,13 @@
 scripts/denoise_oracle.py, the fixture tests/golden/denoise.pt, the header, the CLI flags, the
 argument checks of ops): no GPU."""
 import os
-import re
 import sys
 
 import numpy as np
 import pytest
 import torch
 
+import abi_header as H
 from conftest import load_golden
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -202,17 +202,14 @@ def test_regenerating_a_case_reproduces_the_fixture(dfx):
 
 def test_abi_header_and_makefile_pins():
     from segan_pytorch_amd import _lib, ops
-    hdr = open(os.path.join(ROOT, 'include', 'segan_hip.h')).read()
-    assert '#define SEGAN_ABI_VERSION 17' in hdr and _lib.ABI_VERSION == 17
-    block = hdr[hdr.index('Wiener and log-MMSE baseline enhancers'):
-                hdr.index('int segan_denoise_dims')]
+    assert H.macro('SEGAN_ABI_VERSION') == 17 and _lib.ABI_VERSION == 17
+    block = H.RAW[H.RAW.index('Wiener and log-MMSE baseline enhancers'):
+                  H.RAW.index('int segan_denoise_dims')]
     assert 'Added without a change of SEGAN_ABI_VERSION: the exports\n * are purely additive.' in block
-    assert '#define SEGAN_DENOISE_WIENER {}'.format(ops.DENOISE_RULES['wiener']) in hdr
-    assert '#define SEGAN_DENOISE_LOGMMSE {}'.format(ops.DENOISE_RULES['logmmse']) in hdr
-    code = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
+    assert H.macro('SEGAN_DENOISE_WIENER') == ops.DENOISE_RULES['wiener']
+    assert H.macro('SEGAN_DENOISE_LOGMMSE') == ops.DENOISE_RULES['logmmse']
     for name, nargs in (('segan_denoise_dims', 4), ('segan_denoise', 14)):
-        assert re.search(r'\bint {}\('.format(name), code), name
-        assert len(_lib.SIGNATURES[name][1]) == nargs
+        assert len(H.args(name)) == len(_lib.SIGNATURES[name][1]) == nargs, name
     mk = open(os.path.join(ROOT, 'Makefile')).read()
     assert '$(CSRC)/segan_denoise.hip' in mk.split('SRCS :=')[1].split('\n')[0]
     doc = open(os.path.join(ROOT, 'INTEGRATION.md')).read()

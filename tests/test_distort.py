@@ -4,7 +4,6 @@ fixture tests/golden/distort.pt (recipe scripts/make_golden_distort.py), the dra
 BandLimit / Distort, the loader's selection / naming / hand-over logic with the device ops replaced
 by host stand-ins, the train.py flags and the C ABI."""
 import os
-import re
 import sys
 
 import numpy as np
@@ -12,6 +11,7 @@ import pytest
 import torch
 from scipy.io import wavfile
 
+import abi_header as H
 from conftest import load_golden
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -555,27 +555,23 @@ DISTORT_SYMBOLS = ('segan_clip_rows', 'segan_chop_rows', 'segan_fir_rows')
 
 def test_header_lib_and_abi_agree():
     from segan_pytorch_amd import _lib, ops
-    hdr = open(os.path.join(ROOT, 'include', 'segan_hip.h')).read()
-    assert re.search(r'#define SEGAN_ABI_VERSION 17\b', hdr)
+    assert H.macro('SEGAN_ABI_VERSION') == 17
     for name, val in (('SEGAN_CHOP_MAX', ops.CHOP_MAX), ('SEGAN_FIR_MAX_K', ops.FIR_MAX_K),
                       ('SEGAN_FIR_TILE', ops.FIR_TILE), ('SEGAN_CLIP_ST_SILENT', ops.CLIP_SILENT),
                       ('SEGAN_CLIP_ST_FACTOR', ops.CLIP_FACTOR),
                       ('SEGAN_CHOP_ST_NOLEVEL', ops.CHOP_NOLEVEL), ('SEGAN_FIR_ST_ID', ops.FIR_ID)):
-        assert re.search(r'#define {} {}\b'.format(name, val), hdr), name
+        assert H.macro(name) == val, name
     assert (ops.CHOP_MAX, ops.FIR_MAX_K, ops.FIR_TILE) == (D.CHOP_MAX, D.FIR_MAX_K, G.FIR_TILE)
     assert (ops.CLIP_SILENT, ops.CLIP_FACTOR, ops.CHOP_NOLEVEL) == (
         D.CLIP_SILENT, D.CLIP_FACTOR, D.CHOP_NOLEVEL)
     assert _lib.ABI_VERSION == 17
     lib = _lib.load()
     assert lib.segan_abi_version() == 17
-    code = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
     doc = open(os.path.join(ROOT, 'INTEGRATION.md')).read()
     for name in DISTORT_SYMBOLS:
-        m = re.search(r'\bint ' + name + r'\s*\(([^)]*)\)', code)
-        assert m, name
-        assert len(m.group(1).split(',')) == len(_lib.SIGNATURES[name][1]), name
+        assert len(H.args(name)) == len(_lib.SIGNATURES[name][1]), name
         assert hasattr(lib, name) and name in doc
-    assert 'without a change of SEGAN_ABI_VERSION' in hdr[hdr.index('segan_clip_rows:'):]
+    assert 'without a change of SEGAN_ABI_VERSION' in H.RAW[H.RAW.index('segan_clip_rows:'):]
     # arguments validated before any launch
     buf = torch.zeros(64)
     q = buf.data_ptr()

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_header as H
 from conftest import load_golden
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -145,17 +146,15 @@ def test_fixture_is_small_stores_no_signals_and_bounds_the_tolerances(mfx):
 
 def test_abi_entries_are_additive():
     from segan_pytorch_amd import _lib
-    hdr = open(os.path.join(ROOT, 'include', 'segan_hip.h')).read()
-    assert '#define SEGAN_ABI_VERSION 17' in hdr and _lib.ABI_VERSION == 17
-    code = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
+    assert H.macro('SEGAN_ABI_VERSION') == 17 and _lib.ABI_VERSION == 17
     assert re.search(r'\bint segan_fwsegsnr\(const float\* ref, const float\* deg, const int\* '
                      r'lengths, int rows, int T,\s+int srate, double\* frames_out, double\* '
-                     r'row_out, void\* stream\);', code)
+                     r'row_out, void\* stream\);', H.CODE)
     assert re.search(r'\bint segan_cepdist\(const float\* ref, const float\* deg, const int\* '
-                     r'lengths,', code)
+                     r'lengths,', H.CODE)
     assert re.search(r'\bint segan_sisdr\(const float\* ref, const float\* deg, const int\* '
                      r'lengths, int rows, int T,\s+double\* row_out, double\* ws, void\* '
-                     r'stream\);', code)
+                     r'stream\);', H.CODE)
     for name, nargs in (('segan_fwsegsnr', 9), ('segan_cepdist', 8), ('segan_sisdr', 8)):
         assert len(_lib.SIGNATURES[name][1]) == nargs
     lib = _lib.load()
@@ -170,7 +169,7 @@ def test_abi_entries_are_additive():
     doc = open(os.path.join(ROOT, 'INTEGRATION.md')).read()
     assert all(n in doc for n in ('segan_fwsegsnr', 'segan_cepdist', 'segan_sisdr'))
     from segan_pytorch_amd import ops
-    assert '#define SEGAN_SISDR_SPAN {}'.format(ops.SISDR_SPAN) in hdr
+    assert H.macro('SEGAN_SISDR_SPAN') == ops.SISDR_SPAN
 
 
 def test_eval_cli_flags_and_unchanged_header_line():

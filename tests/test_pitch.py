@@ -3,13 +3,13 @@ scripts/pitch_oracle.py, the fixture tests/golden/pitch.pt, the header, the CLI 
 checks of ops): no GPU."""
 import math
 import os
-import re
 import sys
 
 import numpy as np
 import pytest
 import torch
 
+import abi_header as H
 from conftest import load_golden
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -195,16 +195,13 @@ def test_regenerating_a_small_case_reproduces_the_fixture_bits(pfx):
 
 def test_abi_header_and_makefile_pins():
     from segan_pytorch_amd import _lib, ops
-    hdr = open(os.path.join(ROOT, 'include', 'segan_hip.h')).read()
-    assert '#define SEGAN_ABI_VERSION 17' in hdr and _lib.ABI_VERSION == 17
-    block = hdr[hdr.index('Pitch tracking by YIN'):hdr.index('int segan_pitch_frames')]
+    assert H.macro('SEGAN_ABI_VERSION') == 17 and _lib.ABI_VERSION == 17
+    block = H.RAW[H.RAW.index('Pitch tracking by YIN'):H.RAW.index('int segan_pitch_frames')]
     assert 'Added\n * without a change of SEGAN_ABI_VERSION: the exports are purely additive.' in block
-    assert '#define SEGAN_PITCH_NB {}'.format(ops.PITCH_NB) in hdr and ops.PITCH_NB == O.NB == 5
-    code = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
+    assert H.macro('SEGAN_PITCH_NB') == ops.PITCH_NB and ops.PITCH_NB == O.NB == 5
     for name, nargs in (('segan_pitch_frames', 2), ('segan_pitch_dims', 4), ('segan_pitch', 11),
                         ('segan_pitch_cmnd', 8), ('segan_f0_eval', 9)):
-        assert re.search(r'\bint {}\('.format(name), code), name
-        assert len(_lib.SIGNATURES[name][1]) == nargs
+        assert len(H.args(name)) == len(_lib.SIGNATURES[name][1]) == nargs, name
     mk = open(os.path.join(ROOT, 'Makefile')).read()
     assert '$(CSRC)/segan_pitch.hip' in mk.split('SRCS :=')[1].split('\n')[0]
     doc = open(os.path.join(ROOT, 'INTEGRATION.md')).read()

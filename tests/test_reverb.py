@@ -4,7 +4,6 @@ fixture tests/golden/reverb.pt (recipe scripts/make_golden_reverb.py), RIRBank's
 loader's selection / naming / draw logic with the device ops replaced by host stand-ins, the
 train.py flags and the C ABI."""
 import os
-import re
 import sys
 
 import numpy as np
@@ -12,6 +11,7 @@ import pytest
 import torch
 from scipy.io import wavfile
 
+import abi_header as H
 from conftest import load_golden
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -349,18 +349,14 @@ REVERB_SYMBOLS = ('segan_reverb_dims', 'segan_reverb_basis', 'segan_reverb_bank'
 def test_header_lib_and_abi_agree():
     import ctypes
     from segan_pytorch_amd import _lib, ops
-    hdr = open(os.path.join(ROOT, 'include', 'segan_hip.h')).read()
-    assert re.search(r'#define SEGAN_ABI_VERSION 17\b', hdr)
-    assert re.search(r'#define SEGAN_REVERB_P {}\b'.format(ops.REVERB_P), hdr)
+    assert H.macro('SEGAN_ABI_VERSION') == 17
+    assert H.macro('SEGAN_REVERB_P') == ops.REVERB_P
     assert _lib.ABI_VERSION == 17
     lib = _lib.load()
     assert lib.segan_abi_version() == 17
-    code = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
     doc = open(os.path.join(ROOT, 'INTEGRATION.md')).read()
     for name in REVERB_SYMBOLS:
-        m = re.search(r'\bint ' + name + r'\s*\(([^)]*)\)', code)
-        assert m, name
-        assert len(m.group(1).split(',')) == len(_lib.SIGNATURES[name][1]), name
+        assert len(H.args(name)) == len(_lib.SIGNATURES[name][1]), name
         assert hasattr(lib, name) and name in doc
     # host-only sizing, and arguments validated before any launch
     P = ops.REVERB_P

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_header as H
 from conftest import load_golden
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -136,19 +137,17 @@ def test_fixture_is_small_stores_no_signals_and_bounds_the_tolerance(sfx):
 
 def test_abi_entries_are_additive():
     from segan_pytorch_amd import _lib, ops
-    hdr = open(os.path.join(ROOT, 'include', 'segan_hip.h')).read()
-    assert '#define SEGAN_ABI_VERSION 17' in hdr and _lib.ABI_VERSION == 17
-    code = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
-    assert re.search(r'\bint segan_sdr_dims\(int rows, int T, int taps, long long\* out\);', code)
+    assert H.macro('SEGAN_ABI_VERSION') == 17 and _lib.ABI_VERSION == 17
+    assert re.search(r'\bint segan_sdr_dims\(int rows, int T, int taps, long long\* out\);', H.CODE)
     assert re.search(r'\bint segan_sdr\(const float\* ref, const float\* deg, const int\* lengths, '
                      r'int rows, int T, int taps,\s+double\* row_out, double\* stages_out, '
-                     r'double\* ws, void\* stream\);', code)
+                     r'double\* ws, void\* stream\);', H.CODE)
     assert re.search(r'\bint segan_toeplitz_solve\(const double\* r, const double\* d, int rows, '
-                     r'int n, double\* c_out,\s+int\* order_out, void\* stream\);', code)
+                     r'int n, double\* c_out,\s+int\* order_out, void\* stream\);', H.CODE)
     for name, nargs in (('segan_sdr_dims', 4), ('segan_sdr', 10), ('segan_toeplitz_solve', 7)):
         assert len(_lib.SIGNATURES[name][1]) == nargs
-    assert '#define SEGAN_SDR_SPAN {}'.format(ops.SDR_SPAN) in hdr
-    assert '#define SEGAN_SDR_MAX_TAPS {}'.format(ops.SDR_TAPS) in hdr and ops.SDR_TAPS == 512
+    assert H.macro('SEGAN_SDR_SPAN') == ops.SDR_SPAN
+    assert H.macro('SEGAN_SDR_MAX_TAPS') == ops.SDR_TAPS and ops.SDR_TAPS == 512
     lib = _lib.load()
     assert lib.segan_abi_version() == 17
     # arguments are checked before any launch: no device is needed to be refused

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_header as H
 from conftest import load_golden
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -121,22 +122,20 @@ def test_fixture_is_small_stores_no_signals_and_bounds_the_tolerance(sfx):
 
 def test_abi_entries_are_additive():
     from segan_pytorch_amd import _lib, ops
-    hdr = open(os.path.join(ROOT, 'include', 'segan_hip.h')).read()
-    assert '#define SEGAN_ABI_VERSION 17' in hdr and _lib.ABI_VERSION == 17
-    code = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
+    assert H.macro('SEGAN_ABI_VERSION') == 17 and _lib.ABI_VERSION == 17
     assert re.search(r'\bint segan_fft_z2z\(const double\* in, double\* out, int rows, int log2n, '
-                     r'int inverse,\s+void\* stream\);', code)
-    assert re.search(r'\bint segan_srmr_dims\(int rows, int T, int rate, long long\* out\);', code)
+                     r'int inverse,\s+void\* stream\);', H.CODE)
+    assert re.search(r'\bint segan_srmr_dims\(int rows, int T, int rate, long long\* out\);', H.CODE)
     assert re.search(r'\bint segan_srmr\(const float\* x, const int\* lengths, int rows, int T, '
                      r'int rate,\s+double\* row_out,\s+double\* stages_out, double\* ws, '
-                     r'void\* stream\);', code)
+                     r'void\* stream\);', H.CODE)
     for name, nargs in (('segan_fft_z2z', 6), ('segan_srmr_dims', 4), ('segan_srmr', 9)):
         assert len(_lib.SIGNATURES[name][1]) == nargs
     for macro, value in (('SEGAN_SRMR_CHANNELS', ops.SRMR_CHANNELS),
                          ('SEGAN_SRMR_BANDS', ops.SRMR_BANDS), ('SEGAN_SRMR_STAGE', ops.SRMR_STAGE),
                          ('SEGAN_FFT_LDS_LOG2', ops.FFT_LDS_LOG2),
                          ('SEGAN_FFT_MAX_LOG2', ops.FFT_MAX_LOG2)):
-        assert '#define {} {}'.format(macro, value) in hdr
+        assert H.macro(macro) == value
     assert (ops.SRMR_CHANNELS, ops.SRMR_BANDS, ops.FFT_MAX_LOG2) == (23, 8, 20)
     lib = _lib.load()
     assert lib.segan_abi_version() == 17

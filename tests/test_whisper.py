@@ -16,6 +16,7 @@ import pytest
 import torch
 from scipy.io import wavfile
 
+import abi_header as H
 from conftest import load_golden
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -412,25 +413,21 @@ WHISPER_SYMBOLS = ('segan_whisper_noise', 'segan_whisper_lags', 'segan_whisper_l
 
 def test_header_lib_and_abi_agree():
     from segan_pytorch_amd import _lib, ops
-    hdr = open(os.path.join(ROOT, 'include', 'segan_hip.h')).read()
-    assert re.search(r'#define SEGAN_ABI_VERSION 17\b', hdr)
+    assert H.macro('SEGAN_ABI_VERSION') == 17
     for name, val in (('SEGAN_WHISPER_N', ops.WHISPER_N), ('SEGAN_WHISPER_H', ops.WHISPER_H),
                       ('SEGAN_WHISPER_P', ops.WHISPER_P), ('SEGAN_WHISPER_WU', ops.WHISPER_WU),
                       ('SEGAN_WHISPER_ST_SILENT', ops.WHISPER_SILENT),
                       ('SEGAN_WHISPER_ST_TILT', ops.WHISPER_TILT)):
-        assert re.search(r'#define {} {}\b'.format(name, val), hdr), name
+        assert H.macro(name) == val, name
     assert (ops.WHISPER_SILENT, ops.WHISPER_TILT) == (W.WHISPER_SILENT, W.WHISPER_TILT)
     assert _lib.ABI_VERSION == 17
     lib = _lib.load()
     assert lib.segan_abi_version() == 17
-    code = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
     doc = open(os.path.join(ROOT, 'INTEGRATION.md')).read()
     for name in WHISPER_SYMBOLS + ('segan_whisper_frames', 'segan_whisper_ws_doubles'):
-        m = re.search(r'\b(?:int|long long) ' + name + r'\s*\(([^)]*)\)', code)
-        assert m, name
-        assert len(m.group(1).split(',')) == len(_lib.SIGNATURES[name][1]), name
+        assert len(H.args(name, '(?:int|long long)')) == len(_lib.SIGNATURES[name][1]), name
         assert hasattr(lib, name) and name in doc
-    assert 'without a change of SEGAN_ABI_VERSION' in hdr[hdr.index('segan_whisper_rows:'):]
+    assert 'without a change of SEGAN_ABI_VERSION' in H.RAW[H.RAW.index('segan_whisper_rows:'):]
     assert 'segan_whisper.hip' in open(os.path.join(ROOT, 'Makefile')).read()
     # host arithmetic of the library, and arguments validated before any launch
     assert [lib.segan_whisper_frames(T) for T in (1, 255, 256, 16384)] == [2, 2, 3, 66]
