@@ -4,6 +4,7 @@ the clean wavs of the same names, on the MI355X: the reference's eval_noisy_perf
     python eval_noisy_performance.py --test_wavs DIR --clean_wavs DIR --logfile FILE [--stoi]
                                      [--estoi] [--fwsegsnr] [--cd] [--sisdr] [--sdr] [--srmr]
                                      [--f0] [--resample] [--baseline {wiener,logmmse}]
+                                     [--wpe [--wpe_taps K] [--wpe_delay D] [--wpe_iterations I]]
 
 16 kHz wavs only (int16 files are scaled by 1/32768, float files used as they are), unless
 --resample converts files of other rates to 16 kHz on the GPU first (int16 files to int16, float
@@ -24,7 +25,10 @@ divergence between the log-F0 distributions, on YIN contours tracked on the GPU)
 final mean line over the files where it is finite with the count of NaN files.  --baseline
 {wiener,logmmse} passes every degraded file through that statistical-model enhancer
 (segan_pytorch_amd.baselines, at 16 kHz, float32) before all measures, so that one run gives the
-baseline's row of a results table; the header line and the columns are unchanged."""
+baseline's row of a results table; the header line and the columns are unchanged.  --wpe passes
+every degraded file through the WPE dereverberator (baselines.wpe, at 16 kHz, float32; --wpe_taps,
+--wpe_delay, --wpe_iterations) before all measures, and before the --baseline enhancer if both are
+given; the header line and the columns are unchanged as well."""
 import argparse
 import glob
 import os
@@ -84,6 +88,7 @@ def main(opts):
     from segan_pytorch_amd import baselines, quality
     from segan_pytorch_amd.quality import composite_eval
     baseline = getattr(opts, 'baseline', None)
+    wpe = baselines.wpe_opts(opts)
     extra = [(name, getattr(quality, fn)) for name, flag, fn in EXTRA if getattr(opts, flag)]
     noisy_wavs = sorted(glob.glob(os.path.join(opts.test_wavs, '*.wav')))
     metrics = {'csig': [], 'cbak': [], 'covl': [], 'STOI': [], 'ESTOI': [], 'FWSEGSNR': [],
@@ -98,6 +103,8 @@ def main(opts):
             clean_wav = os.path.join(opts.clean_wavs, bname + '.wav')
             noisy = read_wav(noisy_wav, opts)
             clean = read_wav(clean_wav, opts)
+            if wpe is not None:
+                noisy = baselines.wpe(torch.from_numpy(noisy).cuda(), **wpe).cpu().numpy()
             if baseline is not None:
                 noisy = baselines.denoise(torch.from_numpy(noisy).cuda(),
                                           rule=baseline).cpu().numpy()
@@ -179,8 +186,10 @@ def build_parser():
     parser.add_argument('--resample', action='store_true', default=False,
                         help='convert wavs that are not 16 kHz to 16 kHz on the GPU instead of '
                              'refusing them')
+    from segan_pytorch_amd.baselines import add_wpe_flags
     from segan_pytorch_amd.resample import add_filter_flags
     add_filter_flags(parser)
+    add_wpe_flags(parser)
     return parser
 
 

@@ -1,4 +1,5 @@
-"""ctypes binding of libsegan_hip.so (the C ABI declared in include/segan_hip.h).
+"""ctypes binding of libsegan_hip.so (the C ABI declared in include/segan_hip.h, and the additive
+exports of the extension header include/segan_dereverb.h).
 
 The signatures and the integer macros are read from the header itself, so the binding cannot
 drift from the declarations the HIP sources are compiled against.
@@ -14,6 +15,8 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('SEGAN_HIP_LIB') or os.path.join(_HERE, 'libsegan_hip.so')   # override: A/B of two builds
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'segan_hip.h')
+# exports added beside ABI 17 without touching the main header (the WPE dereverberation baseline)
+EXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'segan_dereverb.h')
 
 
 class SeganSrc(Structure):
@@ -84,16 +87,18 @@ def read_header(text, where='<text>'):
     return signatures, defines
 
 
-def _read_header_file():
-    if not os.path.exists(HEADER_PATH):
+def _read_header_file(path=HEADER_PATH):
+    if not os.path.exists(path):
         raise RuntimeError('segan_pytorch_amd: {} not found. The ctypes binding is read from the '
-                           'header the library is built against.'.format(HEADER_PATH))
-    with open(HEADER_PATH) as f:
-        return read_header(f.read(), HEADER_PATH)
+                           'header the library is built against.'.format(path))
+    with open(path) as f:
+        return read_header(f.read(), path)
 
 
 # name -> (restype, argtypes) of every entry point, and name -> int of every SEGAN_* macro
 SIGNATURES, DEFINES = _read_header_file()
+# the same of the extension header, in tables of their own: SIGNATURES and DEFINES are ABI 17's
+EXT_SIGNATURES, EXT_DEFINES = _read_header_file(EXT_HEADER_PATH)
 
 PAD_REFLECT = DEFINES['SEGAN_PAD_REFLECT']
 PAD_ZERO = DEFINES['SEGAN_PAD_ZERO']
@@ -123,7 +128,7 @@ def load():
     except ImportError:     # pragma: no cover
         pass
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
         fn = getattr(lib, name)      # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

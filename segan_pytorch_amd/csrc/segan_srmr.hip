@@ -8,17 +8,15 @@
 //                         transform, or 2^b interleaved ones (the columns or rows of a two-level
 //                         transform, or short transforms of a batch); twiddle, analytic mask, 1/n
 //                         and magnitude are applied on the way out
+//                         (the passes themselves and the twiddle table: segan_fft_lds.h, shared
+//                         with segan_dereverb.hip)
 //   srmr_gammatone_kernel one lane per (row, channel): four cascaded biquads over the row's
 //                         samples into the complex work buffer, zero-padded to the row's own L
 //   srmr_modulation_kernel  one lane per (row, channel, band): the band-pass over the envelope
 //                         and the windowed squares of the (at most four) frames a sample is in
 //   srmr_final_kernel     one workgroup per row: frame means, shares, BW, K*, the ratio
-#include "segan_signal.h"
+#include "segan_fft_lds.h"
 
-#define FFT_THREADS 256
-#define FFT_LDS_LOG2 SEGAN_FFT_LDS_LOG2
-#define FFT_LDS_N (1 << FFT_LDS_LOG2)
-#define FFT_BFLY (FFT_LDS_N / 2 / FFT_THREADS)   // butterflies a thread holds in registers
 #define SRMR_CH SEGAN_SRMR_CHANNELS
 #define SRMR_BANDS SEGAN_SRMR_BANDS
 #define SRMR_PAIRS (SRMR_CH * SRMR_BANDS)
@@ -26,7 +24,6 @@
 #define SRMR_BLOCK 16       // samples whose loads the gammatone lane issues at once
 #define SRMR_MOD_BLOCK 8    // and the modulation lane
 
-static_assert(FFT_BFLY * 2 * FFT_THREADS == FFT_LDS_N, "fft_kernel: whole butterflies per thread");
 static_assert(SEGAN_FFT_MAX_LOG2 <= 2 * FFT_LDS_LOG2, "fft: two levels reach the largest size");
 static_assert(SEGAN_SRMR_STAGE == 2 * SRMR_CH + SRMR_PAIRS + 4, "srmr: the stage block");
 
@@ -146,12 +143,6 @@ __device__ inline bool srmr_phase(int lg, FftArgs* a) {
   return true;
 }
 
-// (x + i y)(c + i s) with its roundings spelled out: the bits do not hang on what the compiler
-// chooses to contract
-__device__ __forceinline__ double2 cmul(double x, double y, double c, double s) {
-  return make_double2(fma(x, c, -(y * s)), fma(x, s, y * c));
-}
-
 __global__ __launch_bounds__(FFT_THREADS) void fft_kernel(FftArgs a) {
   __shared__ double2 sm[FFT_LDS_N];
   const int tid = threadIdx.x;
@@ -165,7 +156,7 @@ __global__ __launch_bounds__(FFT_THREADS) void fft_kernel(FftArgs a) {
   const FftGeom g = fft_geom(a.lg, a.kind, a.ntrans);
   const long long t0 = (long long)tile << g.lgbatch;
   if (t0 >= g.tcount) return;
-  const int M = 1 << (g.lgsub + g.lgbatch), half = M >> 1;
+  const int M = 1 << (g.lgsub + g.lgbatch);
   const int sub_mask = (1 << g.lgsub) - 1, batch_mask = (1 << g.lgbatch) - 1;
   const double2* in = a.in + wrow * a.ostride;
   double2* out = a.out + wrow * a.ostride;
@@ -179,36 +170,7 @@ __global__ __launch_bounds__(FFT_THREADS) void fft_kernel(FftArgs a) {
   }
   __syncthreads();
 
-  // Stockham: pass p pairs x[j], x[j + M/2] and writes them 2^p transforms' stride apart; the
-  // 2^lgbatch interleaved transforms ride along as the low bits of j
-  for (int pass = 0; pass < g.lgsub; ++pass) {
-    const int lgs = g.lgbatch + pass;
-    double2 y0[FFT_BFLY], y1[FFT_BFLY];
-#pragma unroll
-    for (int u = 0; u < FFT_BFLY; ++u) {
-      const int j = tid + FFT_THREADS * u;
-      if (j < half) {
-        const double2 p0 = sm[j], p1 = sm[j + half];
-        const int p = j >> lgs;
-        const double2 w = a.tw[p << (pass + FFT_LDS_LOG2 - g.lgsub)];
-        const double ws = a.inverse ? w.y : -w.y;
-        const double dx = p0.x - p1.x, dy = p0.y - p1.y;
-        y0[u] = make_double2(p0.x + p1.x, p0.y + p1.y);
-        y1[u] = cmul(dx, dy, w.x, ws);
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < FFT_BFLY; ++u) {
-      const int j = tid + FFT_THREADS * u;
-      if (j < half) {
-        const int p = j >> lgs, q = j & ((1 << lgs) - 1);
-        sm[q + ((2 * p) << lgs)] = y0[u];
-        sm[q + ((2 * p + 1) << lgs)] = y1[u];
-      }
-    }
-    __syncthreads();
-  }
+  fft_lds_passes(sm, a.tw, g.lgsub, g.lgbatch, a.inverse != 0);
 
   const long long n = 1LL << a.lg;
   const double inv_n = 1.0 / (double)n;
@@ -240,26 +202,6 @@ __global__ __launch_bounds__(FFT_THREADS) void fft_kernel(FftArgs a) {
 }
 
 // ---- tables ----
-
-struct FftTable {
-  int device;
-  double2* tw;
-};
-SeganDeviceTables<FftTable> g_fft_tables;
-
-const FftTable* fft_table() {
-  return g_fft_tables.get(
-      "fft", [](const FftTable&) { return true; },
-      [](FftTable* e) {
-        std::vector<double2> tw(FFT_LDS_N / 2);
-        for (int m = 0; m < FFT_LDS_N / 2; ++m) {   // rounded from extended precision
-          const long double ang = 2.0L * 3.14159265358979323846264338327950288L * m / FFT_LDS_N;
-          tw[m] = make_double2((double)cosl(ang), (double)sinl(ang));
-        }
-        tw[FFT_LDS_N / 4] = make_double2(0.0, 1.0);
-        return segan_upload(&e->tw, tw, "fft");
-      });
-}
 
 // doubles of the per-rate table: gammatone [23][10] (b0, b1 of the four sections in running
 // order, a1, a2), modulation [8][4] (b0, b2, a1, a2, all over a0), cutoffs [8], cfs [23],

@@ -1629,6 +1629,109 @@ def denoise_rows(x, lengths=None, srate=16000, rule='logmmse', out_dtype=None,
     return _denoise_run(x, lengths, srate, rule, out_dtype, ws_cap, False)['y']
 
 
+_E = _lib.EXT_DEFINES    # the integer macros of include/segan_dereverb.h
+WPE_RATES = (8000, 16000)
+WPE_MAX_T = 1 << 24
+WPE_MAX_TAPS = _E['SEGAN_WPE_MAX_TAPS']
+WPE_MAX_DELAY = _E['SEGAN_WPE_MAX_DELAY']
+WPE_MAX_ITERATIONS = _E['SEGAN_WPE_MAX_ITERATIONS']
+WPE_TILE = _E['SEGAN_WPE_TILE']            # frames the hot kernel streams a long row with
+WPE_PIVOT = _E['SEGAN_WPE_ST_PIVOT']       # status bit of wpe_rows
+WPE_WS_CAP = 1 << 30         # bytes of workspace one call of segan_wpe may take
+
+
+def wpe_dims(rows, T, srate=16000, taps=10, delay=3):
+    """segan_wpe_dims (host only) as a dict: nfft, hop and bins at `srate`, the frames of a row of
+    T samples, ws_bytes for `rows` rows."""
+    dims = (ctypes.c_int64 * 5)()
+    check(_lib.load().segan_wpe_dims(rows, T, srate, taps, delay, dims), 'wpe')
+    return dict(zip(('nfft', 'hop', 'bins', 'frames', 'ws_bytes'), list(dims)))
+
+
+def _wpe_run(x, lengths, srate, taps, delay, iterations, out_dtype, ws_cap, stages):
+    if not isinstance(x, torch.Tensor):
+        raise TypeError('x must be a tensor, got {}'.format(type(x)))
+    if x.dtype not in _DENOISE_DT:
+        raise TypeError('x must be float32 or float64, got {}'.format(x.dtype))
+    _chk(x, 'x', None, x.dtype)
+    if x.dim() not in (1, 2):
+        raise ValueError('wpe: x must be [rows, T] or [T], got {}'.format(tuple(x.shape)))
+    x2 = x.reshape(-1, x.shape[-1])
+    rows, T = x2.shape
+    if not 1 <= rows <= 65535 or not 1 <= T <= WPE_MAX_T:
+        raise ValueError('wpe: 1 .. 65535 rows of 1 .. 2^24 samples, got {}'.format(tuple(x.shape)))
+    if isinstance(srate, bool) or srate not in WPE_RATES:
+        raise ValueError('wpe: srate must be one of {}, got {!r}'.format(WPE_RATES, srate))
+    taps = _int_arg(taps, 'wpe: taps', 1, WPE_MAX_TAPS)
+    delay = _int_arg(delay, 'wpe: delay', 1, WPE_MAX_DELAY)
+    iterations = _int_arg(iterations, 'wpe: iterations', 0, WPE_MAX_ITERATIONS)
+    out_dtype = x.dtype if out_dtype is None else out_dtype
+    if out_dtype not in _DENOISE_DT:
+        raise ValueError('wpe: out_dtype must be torch.float32 or torch.float64, got '
+                         '{!r}'.format(out_dtype))
+    lens = None if lengths is None else _row_lengths('wpe', lengths, rows, T, x.device)
+    cap = _int_arg(ws_cap, 'wpe: ws_cap', 1, 1 << 62)
+    lib = _lib.load()
+    d = wpe_dims(1, T, srate, taps, delay)
+    per = int(cap // d['ws_bytes'])
+    if per < 1:
+        raise ValueError('wpe: ws_cap of {} bytes is below the {} bytes one row of {} samples '
+                         'needs'.format(cap, d['ws_bytes'], T))
+    per = min(per, rows)
+    ws = _stream_scratch(d['ws_bytes'] * per + 16, x.device)
+    ws = ws[(-ws.data_ptr()) % 16:]
+    F, nfmax = d['bins'], d['frames']
+    y = torch.empty((rows, T), device=x.device, dtype=out_dtype)
+    nframes = torch.empty(rows, device=x.device, dtype=torch.int32)
+    status = torch.empty(rows, device=x.device, dtype=torch.int32)
+    Y = X = g = None
+    if stages:
+        Y = torch.empty((rows, F, nfmax), device=x.device, dtype=torch.complex128)
+        X = torch.empty((rows, F, nfmax), device=x.device, dtype=torch.complex128)
+        g = torch.empty((rows, F, taps), device=x.device, dtype=torch.complex128)
+    for r0 in range(0, rows, per):
+        n = min(per, rows - r0)
+        check(lib.segan_wpe(_ptr(x2[r0:r0 + n]), _DENOISE_DT[x.dtype],
+                            _ptr(None if lens is None else lens[r0:r0 + n]), n, T, srate, taps,
+                            delay, iterations, _ptr(y[r0:r0 + n]), _DENOISE_DT[out_dtype],
+                            _ptr(nframes[r0:r0 + n]), _ptr(status[r0:r0 + n]),
+                            _ptr(None if Y is None else Y[r0:r0 + n]),
+                            _ptr(None if X is None else X[r0:r0 + n]),
+                            _ptr(None if g is None else g[r0:r0 + n]), _ptr(ws), _stream()),
+              'wpe')
+    out = {'y': y.reshape(x.shape), 'nframes': nframes, 'status': status}
+    if stages:
+        out['Y'], out['X'], out['g'] = Y, X, g
+    return out
+
+
+def wpe_stages(x, lengths=None, srate=16000, taps=10, delay=3, iterations=3, out_dtype=None,
+               ws_cap=WPE_WS_CAP):
+    """`wpe_rows` with its stages, as a dict of device tensors: 'y' (shaped
+    like x), 'nframes' [rows] (int32: each row's own frame count), 'status' [rows] (int32: 0, or
+    WPE_PIVOT where a bin's Cholesky met a pivot that is not positive and the bin was left
+    unfiltered), 'Y' and 'X' [rows, bins, nf of T] (complex128: the STFT and the filtered STFT,
+    bin-major, zero from the row's own count on) and 'g' [rows, bins, taps] (complex128: the last
+    prediction filter of every bin; zero for a row returned unchanged)."""
+    return _wpe_run(x, lengths, srate, taps, delay, iterations, out_dtype, ws_cap, True)
+
+
+def wpe_rows(x, lengths=None, srate=16000, taps=10, delay=3, iterations=3, out_dtype=None,
+             ws_cap=WPE_WS_CAP):
+    """The WPE dereverberation (weighted prediction error, Nakatani et al. 2010, single channel)
+    of each row of x ([rows, T] or [T], fp32 or fp64 CUDA tensor) at `srate` (16000 or 8000) on
+    the device, all arithmetic fp64: a 32 ms square-root Hann STFT at a quarter hop, and per bin
+    `iterations` (0 .. 8) rounds of a `taps`-frame (1 .. 32) linear prediction from the frames
+    `delay` (1 .. 8) and more back, weighted by the inverse power of the current estimate, whose
+    prediction is subtracted.  The definition is scripts/wpe_oracle.py.  Row r is
+    x[r, :lengths[r]] (host integers 0 .. T; all T without `lengths`); a row of at most delay +
+    taps frames is returned unchanged; the output is zero from the row's length on, and of
+    `out_dtype` (torch.float32, rounded once, or torch.float64; x's own by default).  The rows are
+    processed in chunks whose workspace stays under `ws_cap` bytes.  Fixed operation order: a
+    batched row equals its own call bit for bit, whatever the chunking."""
+    return _wpe_run(x, lengths, srate, taps, delay, iterations, out_dtype, ws_cap, False)['y']
+
+
 ASL_THRESHOLDS = 15      # nbits - 1 thresholds 2^-15 .. 2^-1 (nbits = 16)
 ADDITIVE_CAP = 1         # status bits of asl_p56 / additive_mix (include/segan_hip.h)
 ADDITIVE_PN0 = 2
