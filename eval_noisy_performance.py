@@ -3,7 +3,8 @@ the clean wavs of the same names, on the MI355X: the reference's eval_noisy_perf
 
     python eval_noisy_performance.py --test_wavs DIR --clean_wavs DIR --logfile FILE [--stoi]
                                      [--estoi] [--fwsegsnr] [--cd] [--sisdr] [--sdr] [--srmr]
-                                     [--f0] [--resample] [--baseline {wiener,logmmse}]
+                                     [--f0 [--f0_tracker {yin,pyin}]] [--resample]
+                                     [--baseline {wiener,logmmse}]
                                      [--wpe [--wpe_taps K] [--wpe_delay D] [--wpe_iterations I]]
 
 16 kHz wavs only (int16 files are scaled by 1/32768, float files used as they are), unless
@@ -22,7 +23,8 @@ speech-to-reverberation modulation energy ratio of the degraded file alone: it n
 signal) and its mean line.  --f0 adds, after every other column, F0MAE, VUV and F0KLD
 (quality.f0_eval: the F0 mean absolute error in Hz, the voiced / unvoiced accuracy and the KL
 divergence between the log-F0 distributions, on YIN contours tracked on the GPU) and, for each, a
-final mean line over the files where it is finite with the count of NaN files.  --baseline
+final mean line over the files where it is finite with the count of NaN files; --f0_tracker pyin
+takes the contours from the Viterbi-smoothed tracker instead (same columns).  --baseline
 {wiener,logmmse} passes every degraded file through that statistical-model enhancer
 (segan_pytorch_amd.baselines, at 16 kHz, float32) before all measures, so that one run gives the
 baseline's row of a results table; the header line and the columns are unchanged.  --wpe passes
@@ -123,7 +125,8 @@ def main(opts):
             if with_f0:
                 L = min(len(clean), len(noisy))
                 f0r = quality.f0_eval(torch.from_numpy(clean[:L]).cuda(),
-                                      torch.from_numpy(noisy[:L]).cuda())
+                                      torch.from_numpy(noisy[:L]).cuda(),
+                                      tracker=getattr(opts, 'f0_tracker', 'yin'))
                 for name, key in F0_COLUMNS:
                     f0_rows[name].append(float(f0r[key][0]))
             end_t = timeit.default_timer()
@@ -180,6 +183,10 @@ def build_parser():
                         help='also compute F0MAE, VUV and F0KLD (F0 mean absolute error in Hz, '
                              'voiced / unvoiced accuracy, KL divergence of the log-F0 '
                              'distributions) on YIN pitch contours')
+    parser.add_argument('--f0_tracker', choices=('yin', 'pyin'), default='yin',
+                        help='the pitch tracker behind --f0: plain YIN, or pyin, its '
+                             'Viterbi-smoothed form, which holds on noisy and whispered input '
+                             '(the columns are the same)')
     parser.add_argument('--baseline', choices=('wiener', 'logmmse'), default=None,
                         help='enhance every degraded file with this statistical-model baseline '
                              'before all measures')

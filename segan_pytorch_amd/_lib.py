@@ -1,5 +1,5 @@
 """ctypes binding of libsegan_hip.so (the C ABI declared in include/segan_hip.h, and the additive
-exports of the extension header include/segan_dereverb.h).
+exports of the extension headers include/segan_dereverb.h and include/segan_pyin.h).
 
 The signatures and the integer macros are read from the header itself, so the binding cannot
 drift from the declarations the HIP sources are compiled against.
@@ -17,6 +17,8 @@ LIB_PATH = os.environ.get('SEGAN_HIP_LIB') or os.path.join(_HERE, 'libsegan_hip.
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'segan_hip.h')
 # exports added beside ABI 17 without touching the main header (the WPE dereverberation baseline)
 EXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'segan_dereverb.h')
+# the same for the Viterbi-smoothed pitch tracker
+PYIN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'segan_pyin.h')
 
 
 class SeganSrc(Structure):
@@ -99,6 +101,7 @@ def _read_header_file(path=HEADER_PATH):
 SIGNATURES, DEFINES = _read_header_file()
 # the same of the extension header, in tables of their own: SIGNATURES and DEFINES are ABI 17's
 EXT_SIGNATURES, EXT_DEFINES = _read_header_file(EXT_HEADER_PATH)
+PYIN_SIGNATURES, PYIN_DEFINES = _read_header_file(PYIN_HEADER_PATH)
 
 PAD_REFLECT = DEFINES['SEGAN_PAD_REFLECT']
 PAD_ZERO = DEFINES['SEGAN_PAD_ZERO']
@@ -128,7 +131,8 @@ def load():
     except ImportError:     # pragma: no cover
         pass
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
+    for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) +
+                              list(PYIN_SIGNATURES.items())):
         fn = getattr(lib, name)      # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

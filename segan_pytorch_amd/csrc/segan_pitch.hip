@@ -21,35 +21,9 @@
 #define PITCH_GROUP 8          // hop blocks per workgroup of pitch_block_kernel
 #define PITCH_FRAMES 16        // frames per workgroup of pitch_frame_kernel
 #define PITCH_THREADS 256
-#define PITCH_MAX_H 80         // the 16 kHz constants; 8 kHz halves them
-#define PITCH_MAX_LAGS 268     // lags 0 .. tau_max + 1
 #define PITCH_LAG_PITCH 269    // odd: the frames' serial walks fall on different LDS banks
-#define PITCH_MAX_T (1 << 24)
 
 namespace {
-
-struct PitchRate {
-  int H, tmin, tmax, nl;   // hop, smallest and largest lag, lags computed (tau_max + 2)
-};
-
-__host__ __device__ inline bool pitch_rate(int srate, PitchRate* p) {
-  if (srate != 16000 && srate != 8000) return false;
-  const int div = srate == 16000 ? 1 : 2;
-  p->H = PITCH_MAX_H / div;
-  p->tmin = 40 / div;
-  p->tmax = 266 / div;
-  p->nl = p->tmax + 2;
-  return true;
-}
-
-// hop blocks of a row of L samples: every index j + tau of a block stays below L
-__host__ __device__ inline int pitch_blocks(int L, int H, int nl) {
-  return L >= nl - 1 ? (L - (nl - 1)) / H : 0;
-}
-
-__host__ __device__ inline int pitch_frames_of(int nb) {
-  return nb >= SEGAN_PITCH_NB ? nb - SEGAN_PITCH_NB + 1 : 0;
-}
 
 // ws[row][nbmax][2][nl]: S then E of each hop block
 __global__ __launch_bounds__(320) void pitch_block_kernel(
@@ -88,11 +62,12 @@ __global__ __launch_bounds__(320) void pitch_block_kernel(
 }
 
 // Frames [16 blockIdx.x, + 16) of row blockIdx.y.  f0 / lag / ap [rows][F] and cmnd [rows][F][nl]
-// may each be NULL; frames from the row's own count on get the fill values (cmnd: NaN).
+// may each be NULL; frames from the row's own count on get the fill values (cmnd: NaN).  ctot
+// [rows][F] (NULL or c(tau_max + 1) of the row's own frames; the others are left alone).
 __global__ __launch_bounds__(PITCH_THREADS) void pitch_frame_kernel(
     const int* __restrict__ lengths, int T, int srate, PitchRate pr, int nbmax, int F, double theta,
     const double* __restrict__ ws, double* __restrict__ f0, int* __restrict__ lag,
-    double* __restrict__ ap, double* __restrict__ cmnd) {
+    double* __restrict__ ap, double* __restrict__ cmnd, double* __restrict__ ctot) {
   __shared__ double dd[PITCH_FRAMES][PITCH_LAG_PITCH];
   __shared__ double clast[PITCH_FRAMES];
   const int r = blockIdx.y, tid = threadIdx.x, nl = pr.nl;
@@ -145,6 +120,7 @@ __global__ __launch_bounds__(PITCH_THREADS) void pitch_frame_kernel(
       dd[tid][tau] = c > 0.0 ? v * (double)tau / c : 1.0;
     }
     clast[tid] = c;
+    if (ctot) ctot[(size_t)r * F + t0 + tid] = c;
   }
   __syncthreads();
   if (cmnd)
@@ -319,13 +295,12 @@ __global__ __launch_bounds__(64) void f0_eval_kernel(
   o[3] = voiced;
 }
 
-bool pitch_sizes_ok(int rows, int T) {
-  return rows > 0 && rows <= 65535 && T > 0 && T <= PITCH_MAX_T;
-}
+bool pitch_sizes_ok(int rows, int T) { return segan_pitch_sizes_ok(rows, T); }
 
 // the two tracking stages; f0 / lag / ap or cmnd may be NULL
 int pitch_run(const float* x, const int* lengths, int rows, int T, int srate, double theta,
-              double* f0, int* lag, double* ap, double* cmnd, double* ws, hipStream_t st) {
+              double* f0, int* lag, double* ap, double* cmnd, double* ctot, double* ws,
+              hipStream_t st) {
   PitchRate pr;
   pitch_rate(srate, &pr);
   const int nbmax = pitch_blocks(T, pr.H, pr.nl), F = pitch_frames_of(nbmax);
@@ -335,11 +310,17 @@ int pitch_run(const float* x, const int* lengths, int rows, int T, int srate, do
   if (int e = segan_check_launch("pitch_block_kernel")) return e;
   hipLaunchKernelGGL(pitch_frame_kernel, dim3(ceil_div(F, PITCH_FRAMES), rows),
                      dim3(PITCH_THREADS), 0, st, lengths, T, srate, pr, nbmax, F, theta,
-                     (const double*)ws, f0, lag, ap, cmnd);
+                     (const double*)ws, f0, lag, ap, cmnd, ctot);
   return segan_check_launch("pitch_frame_kernel");
 }
 
 }  // namespace
+
+int segan_pitch_cmnd_ctot(const float* x, const int* lengths, int rows, int T, int srate,
+                          double* cmnd, double* ctot, double* ws, hipStream_t stream) {
+  return pitch_run(x, lengths, rows, T, srate, 1.0, nullptr, nullptr, nullptr, cmnd, ctot, ws,
+                   stream);
+}
 
 extern "C" int segan_pitch_frames(int T, int srate) {
   PitchRate pr;
@@ -373,7 +354,7 @@ extern "C" int segan_pitch(const float* x, const int* lengths, int rows, int T, 
   SEGAN_REQUIRE(pitch_sizes_ok(rows, T) && pitch_rate(srate, &pr),
                 "pitch: bad sizes rows=%d T=%d srate=%d", rows, T, srate);
   SEGAN_REQUIRE(theta > 0.0 && theta <= 1.0, "pitch: the threshold %g is not in (0, 1]", theta);
-  return pitch_run(x, lengths, rows, T, srate, theta, f0, lag, ap, nullptr, ws,
+  return pitch_run(x, lengths, rows, T, srate, theta, f0, lag, ap, nullptr, nullptr, ws,
                    (hipStream_t)stream);
 }
 
@@ -383,7 +364,7 @@ extern "C" int segan_pitch_cmnd(const float* x, const int* lengths, int rows, in
   SEGAN_REQUIRE(x && cmnd && ws, "pitch: NULL pointer");
   SEGAN_REQUIRE(pitch_sizes_ok(rows, T) && pitch_rate(srate, &pr),
                 "pitch: bad sizes rows=%d T=%d srate=%d", rows, T, srate);
-  return pitch_run(x, lengths, rows, T, srate, 1.0, nullptr, nullptr, nullptr, cmnd, ws,
+  return pitch_run(x, lengths, rows, T, srate, 1.0, nullptr, nullptr, nullptr, cmnd, nullptr, ws,
                    (hipStream_t)stream);
 }
 

@@ -136,6 +136,47 @@ bool segan_upload(V** dst, const std::vector<V>& src, const char* what) {
   return false;
 }
 
+// ---- the framing of the pitch trackers (segan_pitch.hip, segan_pyin.hip) ----
+
+#define PITCH_MAX_H 80         // the 16 kHz constants; 8 kHz halves them
+#define PITCH_MAX_LAGS 268     // lags 0 .. tau_max + 1
+#define PITCH_MAX_T (1 << 24)
+
+struct PitchRate {
+  int H, tmin, tmax, nl;   // hop, smallest and largest lag, lags computed (tau_max + 2)
+};
+
+__host__ __device__ inline bool pitch_rate(int srate, PitchRate* p) {
+  if (srate != 16000 && srate != 8000) return false;
+  const int div = srate == 16000 ? 1 : 2;
+  p->H = PITCH_MAX_H / div;
+  p->tmin = 40 / div;
+  p->tmax = 266 / div;
+  p->nl = p->tmax + 2;
+  return true;
+}
+
+// hop blocks of a row of L samples: every index j + tau of a block stays below L
+__host__ __device__ inline int pitch_blocks(int L, int H, int nl) {
+  return L >= nl - 1 ? (L - (nl - 1)) / H : 0;
+}
+
+__host__ __device__ inline int pitch_frames_of(int nb) {
+  return nb >= SEGAN_PITCH_NB ? nb - SEGAN_PITCH_NB + 1 : 0;
+}
+
+inline bool segan_pitch_sizes_ok(int rows, int T) {
+  return rows > 0 && rows <= 65535 && T > 0 && T <= PITCH_MAX_T;
+}
+
+// ---- defined in segan_pitch.hip ----
+
+// segan_pitch_cmnd with c(tau_max + 1) of every frame of a row's own count as well: cmnd
+// [rows][F][nl], ctot [rows][F] (frames past a row's count are not written), ws as segan_pitch's.
+// The arguments are the caller's to check.
+int segan_pitch_cmnd_ctot(const float* x, const int* lengths, int rows, int T, int srate,
+                          double* cmnd, double* ctot, double* ws, hipStream_t stream);
+
 // ---- defined in segan_resample.hip ----
 
 // p / q = num / den in lowest terms

@@ -429,8 +429,9 @@ class SEGAN(Model):
         `opts.eval_srmr` the key 'srmr' (quality.srmr) is the speech-to-reverberation modulation
         energy ratio of the enhanced (noisy) signal alone: it uses no clean signal.  With
         `opts.eval_f0` (train.py --eval_f0) the keys 'f0_mae', 'vuv_acc', 'f0_kld' (quality.f0_eval:
-        F0 error in Hz, voiced / unvoiced accuracy and log-F0 KL divergence on YIN contours) are
-        added, computed on the same signals; a value is NaN where the measure is undefined.
+        F0 error in Hz, voiced / unvoiced accuracy and log-F0 KL divergence on YIN contours, or
+        on the Viterbi-smoothed ones with `opts.eval_f0_tracker` = 'pyin') are added, computed on
+        the same signals; a value is NaN where the measure is undefined.
         De-emphasis runs along time (the reference applies it along axis 0 of the [B, T] batch,
         model.py:474-477)."""
         from .. import ops, quality
@@ -476,7 +477,8 @@ class SEGAN(Model):
                     if with_srmr:
                         dst['srmr'] += quality.srmr(d).cpu().tolist()
                     if f0_keys:
-                        f0r = quality.f0_eval(c, d)
+                        f0r = quality.f0_eval(c, d, tracker=getattr(opts, 'eval_f0_tracker',
+                                                                    'yin'))
                         for k in f0_keys:
                             dst[k] += f0r[k].cpu().tolist()
                 if bidx >= max_samples:

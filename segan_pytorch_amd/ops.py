@@ -1532,7 +1532,114 @@ def f0_eval(f0_ref, lag_ref, f0_deg, lag_deg, nframes=None):
     return out
 
 
-DENOISE_RULES = {'wiener': _D['SEGAN_DENOISE_WIENER'], 'logmmse': _D['SEGAN_DENOISE_LOGMMSE']}
+_P = _lib.PYIN_DEFINES    # the integer macros of include/segan_pyin.h
+PYIN_NTHETA = _P['SEGAN_PYIN_NTHETA']
+PYIN_BINS = _P['SEGAN_PYIN_BINS']
+PYIN_W = _P['SEGAN_PYIN_W']
+PYIN_WS_CAP = 1 << 30    # bytes of workspace one call of segan_pyin may take
+
+
+def _pyin_srate(srate):
+    if isinstance(srate, bool) or srate not in PITCH_RATES:
+        raise ValueError('pyin: srate must be one of {}, got {!r}'.format(PITCH_RATES, srate))
+
+
+def pyin_tables(srate=16000):
+    """segan_pyin_tables (host only) as a dict of numpy fp64 arrays, the bits the kernels read:
+    'C' [101], the running sum of the thresholds' Beta(2, 18) weights; 'edge' [166], the bin edges
+    as periods in samples at `srate`, descending; 'A' [2, 23], the transition weights (stay,
+    switch) by band offset."""
+    import numpy as np
+    _pyin_srate(srate)
+    C = np.zeros(PYIN_NTHETA + 1, np.float64)
+    edge = np.zeros(PYIN_BINS + 1, np.float64)
+    A = np.zeros((2, 2 * PYIN_W + 1), np.float64)
+    check(_lib.load().segan_pyin_tables(srate, C.ctypes.data, edge.ctypes.data, A.ctypes.data),
+          'pyin_tables')
+    return {'C': C, 'edge': edge, 'A': A}
+
+
+def pyin_dims(rows, T, srate=16000):
+    """segan_pyin_dims (host only) as a dict: frames of a row of T samples, ws_doubles for `rows`
+    rows."""
+    dims = (ctypes.c_int64 * 2)()
+    check(_lib.load().segan_pyin_dims(rows, T, srate, dims), 'pyin')
+    return dict(zip(('frames', 'ws_doubles'), list(dims)))
+
+
+def _pyin_run(x, lengths, srate, ws_cap, stages):
+    _chk(x, 'x', 2)
+    rows, T = x.shape
+    if not 1 <= rows <= 65535 or not 1 <= T <= PITCH_MAX_T:
+        raise ValueError('pyin: 1 .. 65535 rows of 1 .. 2^24 samples, got {}'.format(
+            tuple(x.shape)))
+    _pyin_srate(srate)
+    lens = None if lengths is None else _row_lengths('pyin', lengths, rows, T, x.device)
+    cap = _int_arg(ws_cap, 'pyin: ws_cap', 1, 1 << 62)
+    lib = _lib.load()
+    d = pyin_dims(1, T, srate)
+    F = d['frames']
+    per = int(cap // max(8 * d['ws_doubles'], 1))
+    if per < 1:
+        raise ValueError('pyin: ws_cap of {} bytes is below the {} bytes one row of {} samples '
+                         'needs'.format(cap, 8 * d['ws_doubles'], T))
+    per = min(per, rows)
+    ws = _stream_scratch(max(8 * d['ws_doubles'] * per, 8), x.device)
+    f64 = dict(device=x.device, dtype=torch.float64)
+    i32 = dict(device=x.device, dtype=torch.int32)
+    Fa = max(F, 1)
+    f0 = torch.empty((rows, Fa), **f64)
+    vp = torch.empty((rows, Fa), **f64)
+    lag = torch.empty((rows, Fa), **i32)
+    bv = torch.empty((rows, Fa, PYIN_BINS), **f64) if stages else None
+    state = torch.empty((rows, Fa), **i32) if stages else None
+    delta = torch.empty((rows, 2 * PYIN_BINS), **f64) if stages else None
+    for r0 in range(0, rows, per):
+        n = min(per, rows - r0)
+        sl = slice(r0, r0 + n)
+        check(lib.segan_pyin(_ptr(x[sl]), _ptr(None if lens is None else lens[sl]), n, T, srate,
+                             _ptr(f0[sl]), _ptr(lag[sl]), _ptr(vp[sl]),
+                             _ptr(bv[sl]) if stages else None,
+                             _ptr(state[sl]) if stages else None,
+                             _ptr(delta[sl]) if stages else None, _ptr(ws), _stream()), 'pyin')
+    if lens is None:
+        nframes = torch.full((rows,), F, **i32)
+    else:
+        host = lens.cpu().tolist()
+        nframes = torch.tensor([lib.segan_pitch_frames(L, srate) for L in host],
+                               dtype=torch.int32).to(x.device)
+    out = {'f0': f0[:, :F], 'lag': lag[:, :F], 'vprob': vp[:, :F], 'nframes': nframes}
+    if stages:
+        out.update(bv=bv[:, :F], state=state[:, :F], delta=delta)
+    return out
+
+
+def pyin_stages(x, lengths=None, srate=16000, ws_cap=PYIN_WS_CAP):
+    """`pyin` with its intermediates as a dict of device tensors: 'f0',
+    'lag', 'vprob' [rows, F], 'nframes' [rows] (int32), 'bv' [rows, F, 165] (the voiced
+    observation of every frame and bin, NaN from the row's own frame count on), 'state' [rows, F]
+    (int32: the decoded state, bin m when voiced and 165 + m when unvoiced, -1 from the row's count
+    on) and 'delta' [rows, 330] (the last frame's scaled Viterbi values, NaN for a row without a
+    frame)."""
+    return _pyin_run(x, lengths, srate, ws_cap, True)
+
+
+def pyin(x, lengths=None, srate=16000, ws_cap=PYIN_WS_CAP):
+    """The Viterbi-smoothed pitch contour of each row of x [rows, T] (fp32 CUDA tensor) at `srate`
+    (16000 or 8000): pYIN (Mauch & Dixon 2014) on `pitch`'s framing, fp64 on the device: YIN
+    candidates under 100 thresholds with a Beta(2, 18) prior, then a hidden Markov model over 165
+    pitch bins (5 per semitone from 60 Hz) x {voiced, unvoiced} decoded by Viterbi.  Returns (f0
+    [rows, F] in Hz, 0 when unvoiced; lag [rows, F] int32, the period picked in samples, 0 when
+    unvoiced; vprob [rows, F], the frame's probability of being voiced before the decoding;
+    nframes [rows] int32) under `pitch`'s contract, so `f0_eval` takes f0 and lag unchanged:
+    frames from the row's own count on hold f0 = 0, lag = -1, vprob = NaN.  `lengths` and `ws_cap`
+    as for `pitch`.  Fixed operation order: a batched row equals its own call bit for bit, and a
+    row times a power of two gives the same bits."""
+    out = _pyin_run(x, lengths, srate, ws_cap, False)
+    return out['f0'], out['lag'], out['vprob'], out['nframes']
+
+
+DENOISE_RULES ={'wiener': _D['SEGAN_DENOISE_WIENER'], 'logmmse': _D['SEGAN_DENOISE_LOGMMSE']}
 DENOISE_RATES = (8000, 16000)
 DENOISE_MAX_T = 1 << 24
 DENOISE_WS_CAP = 1 << 30     # bytes of workspace one call of segan_denoise may take

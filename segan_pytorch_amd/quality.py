@@ -257,18 +257,38 @@ def srmr(x, srate=16000, lengths=None):
     return ops.srmr(_as_rows(x, 'x').float().contiguous(), lengths, srate)
 
 
-def pitch(x, srate=16000, lengths=None, threshold=ops.PITCH_THETA):
+TRACKERS = ('yin', 'pyin')
+
+
+def _tracker(tracker):
+    if tracker not in TRACKERS:
+        raise ValueError('tracker must be one of {}, got {!r}'.format(TRACKERS, tracker))
+    return tracker
+
+
+def _track(x, lengths, srate, threshold, tracker):
+    """(f0, lag, ap or vprob, nframes) of ops.pitch or ops.pyin"""
+    if tracker == 'pyin':
+        return ops.pyin(x, lengths, srate)
+    return ops.pitch(x, lengths, srate, threshold)
+
+
+def pitch(x, srate=16000, lengths=None, threshold=ops.PITCH_THETA, tracker='yin'):
     """The pitch contour of each row of x ([T] or [rows, T], fp32 on the device) at `srate` (16000
     or 8000) by YIN with a 5 ms hop: (f0 fp64 [rows, F] in Hz, 0 where
     unvoiced; voiced bool [rows, F]; ap fp64 [rows, F], the normalised difference at the pick,
     small for a clearly periodic frame).  `lengths`: per-row sample counts 0 .. T; frames from a
     row's own count on are unvoiced with ap = NaN.  A row shorter than 667 samples at 16 kHz has
-    no frame."""
-    f0, lag, ap, _ = ops.pitch(_as_rows(x, 'x').float().contiguous(), lengths, srate, threshold)
+    no frame.  tracker='pyin': the Viterbi-smoothed contour on the same frames (DESIGN.md section
+    22; `threshold` does not apply), and the third value is vprob, the frame's probability of
+    being voiced before the decoding."""
+    _tracker(tracker)
+    f0, lag, ap, _ = _track(_as_rows(x, 'x').float().contiguous(), lengths, srate, threshold,
+                            tracker)
     return f0, lag > 0, ap
 
 
-def f0_eval(ref, deg, srate=SRATE, lengths=None, threshold=ops.PITCH_THETA):
+def f0_eval(ref, deg, srate=SRATE, lengths=None, threshold=ops.PITCH_THETA, tracker='yin'):
     """Whether the processed signal has the clean one's pitch: the F0 / voicing measures of the
     reference's F0Evaluator on the YIN contours (`pitch`) of each row of ref / deg (the argument
     contract of `stoi`: the same shape or ValueError, `lengths` per row), as a dict of fp64 tensors
@@ -277,9 +297,12 @@ def f0_eval(ref, deg, srate=SRATE, lengths=None, threshold=ops.PITCH_THETA):
     two log-f0 distributions) and 'voiced' (the clean signal's share of voiced frames).  NaN where
     a measure is undefined: no frame; for f0_mae and f0_kld a signal without a voiced frame
     (DESIGN.md section 19).  The contours are YIN's, not Ahocoder's: the numbers compare systems
-    evaluated with this tool, not with tables made with Ahocoder."""
+    evaluated with this tool, not with tables made with Ahocoder.  tracker='pyin' takes both
+    contours from the Viterbi-smoothed tracker, which holds on noisy and
+    whispered input where YIN's fixed threshold gives way."""
+    _tracker(tracker)
     ref, deg = _same_shape_rows('f0_eval', ref, deg)
-    fr, lr, _, nfr = ops.pitch(ref, lengths, srate, threshold)
-    fd, ld, _, _ = ops.pitch(deg, lengths, srate, threshold)
+    fr, lr, _, nfr = _track(ref, lengths, srate, threshold, tracker)
+    fd, ld, _, _ = _track(deg, lengths, srate, threshold, tracker)
     out = ops.f0_eval(fr, lr, fd, ld, nfr)
     return {'f0_mae': out[:, 0], 'vuv_acc': out[:, 1], 'f0_kld': out[:, 2], 'voiced': out[:, 3]}

@@ -108,6 +108,9 @@ FLAGS = [
                             'unvoiced accuracy and the log-F0 KL divergence (f0_mae, vuv_acc, '
                             'f0_kld) on YIN pitch contours; the validation objective stays '
                             'SSNR')),
+    ('--eval_f0_tracker', dict(choices=('yin', 'pyin'), default='yin',
+                               help='the pitch tracker behind --eval_f0: plain YIN, or pyin, its '
+                                    'Viterbi-smoothed form (the keys are the same)')),
     ('--slice_workers', dict(type=int, default=1)),
     ('--num_workers', dict(type=int, default=1)),
     ('--no-cuda', dict(action='store_true', default=False)),
