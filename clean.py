@@ -27,6 +27,13 @@ and --srmr apply as above.
 works like --baseline: no --cfg_file, no checkpoint, no normalisation.  With --baseline RULE the
 file goes through WPE first and the denoiser after it, the usual chain on reverberant and noisy
 speech.  With --cfg_file it is refused: a generator is trained on its own input.
+
+    python clean.py --omlsa --test_files noisy_dir --synthesis_path out --cuda
+
+--omlsa enhances with OM-LSA on an IMCRA noise estimate (baselines.omlsa_wav), which follows a
+noise level that changes and takes no noise segment from the start of the file.  It works like
+--baseline (no --cfg_file, no checkpoint, no normalisation), runs after --wpe if both are given,
+and is refused together with --baseline or --cfg_file.
 """
 import argparse
 import glob
@@ -80,6 +87,7 @@ def build_parser():
                    help='enhance with this statistical-model baseline instead of a generator; '
                         'needs neither --cfg_file nor --g_pretrained_ckpt')
     baselines.add_wpe_flags(p)
+    baselines.add_omlsa_flags(p)
     return p
 
 
@@ -97,7 +105,10 @@ def main(opts):
     if wpe is not None and opts.cfg_file is not None:
         raise SystemExit('--wpe does not go with --cfg_file: it runs alone or before --baseline, '
                          'not in front of a generator')
-    classical = baseline is not None or wpe is not None
+    omlsa = baselines.omlsa_opts(opts)
+    if omlsa and opts.cfg_file is not None:
+        raise SystemExit('--omlsa does not go with --cfg_file: it is an enhancer of its own')
+    classical = baseline is not None or wpe is not None or omlsa
     if classical:
         if opts.test_files is None:
             raise SystemExit('--test_files is required')
@@ -143,6 +154,8 @@ def main(opts):
                 g_wav = baselines.wpe_wav(g_wav, **wpe)
             if baseline is not None:
                 g_wav = baselines.denoise_wav(g_wav, baseline)
+            if omlsa:
+                g_wav = baselines.omlsa_wav(g_wav)
         if with_srmr:
             from segan_pytorch_amd import quality
             f_wav = g_wav / 32768 if g_wav.dtype == np.int16 else g_wav

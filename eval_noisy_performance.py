@@ -6,6 +6,7 @@ the clean wavs of the same names, on the MI355X: the reference's eval_noisy_perf
                                      [--f0 [--f0_tracker {yin,pyin}]] [--resample]
                                      [--baseline {wiener,logmmse}]
                                      [--wpe [--wpe_taps K] [--wpe_delay D] [--wpe_iterations I]]
+                                     [--omlsa]
 
 16 kHz wavs only (int16 files are scaled by 1/32768, float files used as they are), unless
 --resample converts files of other rates to 16 kHz on the GPU first (int16 files to int16, float
@@ -30,7 +31,10 @@ takes the contours from the Viterbi-smoothed tracker instead (same columns).  --
 baseline's row of a results table; the header line and the columns are unchanged.  --wpe passes
 every degraded file through the WPE dereverberator (baselines.wpe, at 16 kHz, float32; --wpe_taps,
 --wpe_delay, --wpe_iterations) before all measures, and before the --baseline enhancer if both are
-given; the header line and the columns are unchanged as well."""
+given; the header line and the columns are unchanged as well.  --omlsa passes every degraded file
+through the OM-LSA enhancer with IMCRA noise tracking (baselines.omlsa, at 16 kHz, float32) before
+all measures, after --wpe if both are given; with --baseline it is refused; the header line and the
+columns are unchanged."""
 import argparse
 import glob
 import os
@@ -84,6 +88,8 @@ def header_line(opts):
 
 
 def main(opts):
+    from segan_pytorch_amd.baselines import omlsa_opts
+    omlsa = omlsa_opts(opts)         # refuses --omlsa with --baseline before any device is asked for
     if not torch.cuda.is_available():
         raise SystemExit('segan_pytorch_amd runs only on an MI355X (HIP) device; pass --cuda on a '
                          'GPU machine (there is no CPU fallback)')
@@ -110,6 +116,8 @@ def main(opts):
             if baseline is not None:
                 noisy = baselines.denoise(torch.from_numpy(noisy).cuda(),
                                           rule=baseline).cpu().numpy()
+            if omlsa:
+                noisy = baselines.omlsa(torch.from_numpy(noisy).cuda()).cpu().numpy()
             beg_t = timeit.default_timer()
             r = composite_eval(torch.from_numpy(clean).cuda(), torch.from_numpy(noisy).cuda())
             csig, cbak, covl, pesq, ssnr = (float(r[k][0]) for k in
@@ -193,10 +201,11 @@ def build_parser():
     parser.add_argument('--resample', action='store_true', default=False,
                         help='convert wavs that are not 16 kHz to 16 kHz on the GPU instead of '
                              'refusing them')
-    from segan_pytorch_amd.baselines import add_wpe_flags
+    from segan_pytorch_amd.baselines import add_omlsa_flags, add_wpe_flags
     from segan_pytorch_amd.resample import add_filter_flags
     add_filter_flags(parser)
     add_wpe_flags(parser)
+    add_omlsa_flags(parser)
     return parser
 
 

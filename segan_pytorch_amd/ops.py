@@ -1736,7 +1736,102 @@ def denoise_rows(x, lengths=None, srate=16000, rule='logmmse', out_dtype=None,
     return _denoise_run(x, lengths, srate, rule, out_dtype, ws_cap, False)['y']
 
 
-_E = _lib.EXT_DEFINES    # the integer macros of include/segan_dereverb.h
+_O = _lib.OMLSA_DEFINES  # the integer macros of include/segan_omlsa.h
+OMLSA_U = _O['SEGAN_OMLSA_U']    # slots of the minimum window
+OMLSA_V = _O['SEGAN_OMLSA_V']    # frames per slot
+OMLSA_WS_CAP = 1 << 30       # bytes of workspace one call of segan_omlsa may take
+
+
+def omlsa_dims(rows, T, srate=16000):
+    """segan_omlsa_dims (host only) as a dict: frame, hop and nfft at `srate`, the frames of a row
+    of T samples, ws_bytes for `rows` rows."""
+    dims = (ctypes.c_int64 * 5)()
+    check(_lib.load().segan_omlsa_dims(rows, T, srate, dims), 'omlsa')
+    return dict(zip(('frame', 'hop', 'nfft', 'frames', 'ws_bytes'), list(dims)))
+
+
+def _omlsa_run(x, lengths, srate, out_dtype, ws_cap, stages):
+    if not isinstance(x, torch.Tensor):
+        raise TypeError('x must be a tensor, got {}'.format(type(x)))
+    if x.dtype not in _DENOISE_DT:
+        raise TypeError('x must be float32 or float64, got {}'.format(x.dtype))
+    _chk(x, 'x', None, x.dtype)
+    if x.dim() not in (1, 2):
+        raise ValueError('omlsa: x must be [rows, T] or [T], got {}'.format(tuple(x.shape)))
+    x2 = x.reshape(-1, x.shape[-1])
+    rows, T = x2.shape
+    if not 1 <= rows <= 65535 or not 1 <= T <= DENOISE_MAX_T:
+        raise ValueError('omlsa: 1 .. 65535 rows of 1 .. 2^24 samples, got {}'.format(
+            tuple(x.shape)))
+    if isinstance(srate, bool) or srate not in DENOISE_RATES:
+        raise ValueError('omlsa: srate must be one of {}, got {!r}'.format(DENOISE_RATES, srate))
+    out_dtype = x.dtype if out_dtype is None else out_dtype
+    if out_dtype not in _DENOISE_DT:
+        raise ValueError('omlsa: out_dtype must be torch.float32 or torch.float64, got '
+                         '{!r}'.format(out_dtype))
+    lens = None if lengths is None else _row_lengths('omlsa', lengths, rows, T, x.device)
+    cap = _int_arg(ws_cap, 'omlsa: ws_cap', 1, 1 << 62)
+    lib = _lib.load()
+    d = omlsa_dims(1, T, srate)
+    per = int(cap // d['ws_bytes'])
+    if per < 1:
+        raise ValueError('omlsa: ws_cap of {} bytes is below the {} bytes one row of {} samples '
+                         'needs'.format(cap, d['ws_bytes'], T))
+    per = min(per, rows)
+    ws = _stream_scratch(d['ws_bytes'] * per + 16, x.device)
+    ws = ws[(-ws.data_ptr()) % 16:]
+    F, nfmax = d['frame'], d['frames']
+    y = torch.empty((rows, T), device=x.device, dtype=out_dtype)
+    nframes = torch.empty(rows, device=x.device, dtype=torch.int32)
+    pres = rough = noise = None
+    if stages:
+        pres = torch.empty((rows, max(nfmax, 1)), device=x.device, dtype=torch.float64)
+        rough = torch.empty((rows, max(nfmax, 1)), device=x.device, dtype=torch.int32)
+        noise = torch.empty((rows, F + 1), device=x.device, dtype=torch.float64)
+    for r0 in range(0, rows, per):
+        n = min(per, rows - r0)
+        check(lib.segan_omlsa(_ptr(x2[r0:r0 + n]), _DENOISE_DT[x.dtype],
+                              _ptr(None if lens is None else lens[r0:r0 + n]), n, T, srate,
+                              _ptr(y[r0:r0 + n]), _DENOISE_DT[out_dtype],
+                              _ptr(nframes[r0:r0 + n]),
+                              _ptr(None if pres is None else pres[r0:r0 + n]),
+                              _ptr(None if rough is None else rough[r0:r0 + n]),
+                              _ptr(None if noise is None else noise[r0:r0 + n]), _ptr(ws),
+                              _stream()), 'omlsa')
+    out = {'y': y.reshape(x.shape), 'nframes': nframes}
+    if stages:
+        out['presence'], out['rough'], out['noise'] = pres[:, :nfmax], rough[:, :nfmax], noise
+    return out
+
+
+def omlsa_stages(x, lengths=None, srate=16000, out_dtype=None, ws_cap=OMLSA_WS_CAP):
+    """`omlsa_rows` with what its decisions rest on, as a dict of device
+    tensors: 'y' (shaped like x), 'nframes' [rows] (int32: each row's own frame count, 0 for a row
+    returned unchanged), 'presence' [rows, nf of T] (fp64: the weighted mean over the bins of the
+    speech-presence probability p of the frame; NaN from the row's own count on), 'rough'
+    [rows, nf of T] (int32: the bins that the rough decision of the first iteration called noise;
+    -1 from the row's own count on) and 'noise' [rows, frame + 1] (fp64: the noise spectrum as the
+    row's last frame used it; NaN for a row without frames)."""
+    return _omlsa_run(x, lengths, srate, out_dtype, ws_cap, True)
+
+
+def omlsa_rows(x, lengths=None, srate=16000, out_dtype=None, ws_cap=OMLSA_WS_CAP):
+    """The OM-LSA enhancement (Cohen & Berdugo 2001) of each row of x ([rows, T] or [T], fp32 or
+    fp64 CUDA tensor) at `srate` (16000 or 8000) on the device, all arithmetic fp64: the framing
+    of `denoise_rows`, the log-spectral-amplitude gain weighted with the speech-presence
+    probability, and the noise spectrum of IMCRA (Cohen 2003), which follows the minima of the
+    smoothed periodogram over the last OMLSA_U * OMLSA_V frames and so needs no leading noise
+    segment and keeps adapting when the level of the noise changes.  The definition is
+    scripts/omlsa_oracle.py.  Row r is x[r, :lengths[r]] (host integers 0 .. T; all T without
+    `lengths`); a row shorter than 120 ms is returned unchanged; the output is zero from
+    (nframes + 1) hops on, and of `out_dtype` (torch.float32, rounded once, or torch.float64; x's
+    own by default).  The rows are processed in chunks whose workspace stays under `ws_cap`
+    bytes.  Fixed operation order: a batched row equals its own call bit for bit, whatever the
+    chunking."""
+    return _omlsa_run(x, lengths, srate, out_dtype, ws_cap, False)['y']
+
+
+_E = _lib.EXT_DEFINES   # the integer macros of include/segan_dereverb.h
 WPE_RATES = (8000, 16000)
 WPE_MAX_T = 1 << 24
 WPE_MAX_TAPS = _E['SEGAN_WPE_MAX_TAPS']
