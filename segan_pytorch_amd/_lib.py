@@ -1,6 +1,6 @@
 """ctypes binding of libsegan_hip.so (the C ABI declared in include/segan_hip.h, and the additive
-exports of the extension headers include/segan_dereverb.h, include/segan_pyin.h and
-include/segan_omlsa.h).
+exports of the extension headers include/segan_dereverb.h, include/segan_pyin.h,
+include/segan_omlsa.h and include/segan_rir.h).
 
 The signatures and the integer macros are read from the header itself, so the binding cannot
 drift from the declarations the HIP sources are compiled against.
@@ -22,6 +22,8 @@ EXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'segan_derever
 PYIN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'segan_pyin.h')
 # and for the OM-LSA enhancer
 OMLSA_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'segan_omlsa.h')
+# and for the room-impulse-response synthesis
+RIR_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'segan_rir.h')
 
 
 class SeganSrc(Structure):
@@ -106,6 +108,7 @@ SIGNATURES, DEFINES = _read_header_file()
 EXT_SIGNATURES, EXT_DEFINES = _read_header_file(EXT_HEADER_PATH)
 PYIN_SIGNATURES, PYIN_DEFINES = _read_header_file(PYIN_HEADER_PATH)
 OMLSA_SIGNATURES, OMLSA_DEFINES = _read_header_file(OMLSA_HEADER_PATH)
+RIR_SIGNATURES, RIR_DEFINES = _read_header_file(RIR_HEADER_PATH)
 
 PAD_REFLECT = DEFINES['SEGAN_PAD_REFLECT']
 PAD_ZERO = DEFINES['SEGAN_PAD_ZERO']
@@ -136,7 +139,8 @@ def load():
         pass
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) +
-                              list(PYIN_SIGNATURES.items()) + list(OMLSA_SIGNATURES.items())):
+                              list(PYIN_SIGNATURES.items()) + list(OMLSA_SIGNATURES.items()) +
+                              list(RIR_SIGNATURES.items())):
         fn = getattr(lib, name)      # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

@@ -6,7 +6,9 @@ HIP kernels (`ops.asl_p56`, `ops.additive_mix`), batched.  And on-the-fly reverb
 `ops.clip_rows`), `Chop` (chunks of speech removed, `ops.chop_rows`), `BandLimit` (a zero-phase
 low-pass, `ops.fir_rows`), and `Distort`, which applies one of them per row.  And whispered speech
 (section 18): `Whisper` replaces the voiced excitation by noise under the same spectral envelope
-(`ops.whisper_rows`)."""
+(`ops.whisper_rows`).  And synthetic rooms (section 24): `draw_rooms` and `RIRBank.synthetic` make a
+bank of shoebox-room responses by the image-source method (`ops.rir_shoebox`), so that `Reverb`
+needs no measured responses."""
 import glob
 import os
 
@@ -215,6 +217,59 @@ class Additive(object):
         return _one_wave(self.mix, wav, srate=srate)
 
 
+def beta_from_rt60(room, rt60):
+    """One reflection coefficient for all six walls of a shoebox `room` ([.., 3] metres) from a
+    nominal reverberation time `rt60` (seconds) by Sabine's formula: the mean absorption is
+    (24 ln 10 / c) V / (S rt60) with c = 343 m/s, and beta = sqrt(max(1 - absorption, 0)).  Nominal:
+    the image-source response of such a room decays more slowly than diffuse-field theory says, its
+    Schroeder T30 was 1.2 to 1.4 times `rt60` where measured."""
+    room = np.asarray(room, np.float64)
+    rt60 = np.asarray(rt60, np.float64)
+    if room.shape[-1:] != (3,) or np.any(room <= 0) or np.any(rt60 <= 0):
+        raise ValueError('beta_from_rt60: positive sides [.., 3] and a positive rt60 expected')
+    lx, ly, lz = room[..., 0], room[..., 1], room[..., 2]
+    volume = lx * ly * lz
+    surface = 2.0 * (lx * ly + ly * lz + lx * lz)
+    absorption = (24.0 * np.log(10.0) / ops.RIR_C) * volume / (surface * rt60)
+    return np.sqrt(np.maximum(1.0 - absorption, 0.0))
+
+
+def draw_rooms(rng, count, rt60=(0.2, 0.8), room_min=(3, 3, 2.5), room_max=(10, 8, 4),
+               wall_margin=0.5, min_dist=0.5):
+    """`count` shoebox rooms from the numpy Generator `rng`, host only.  Room after room, every
+    draw uniform and in this order: the nominal rt60 in [rt60[0], rt60[1]]; the three sides in
+    [room_min, room_max]; then the three coordinates of the source and the three of the receiver,
+    each in [wall_margin, side - wall_margin], the six drawn again until the two are at least
+    `min_dist` metres apart.  Returns a dict of fp64 arrays: 'room', 'src', 'mic' [count, 3],
+    'rt60' [count] and 'beta' [count, 6] (`beta_from_rt60`, the same on the six walls)."""
+    count = int(count)
+    lo, hi = float(rt60[0]), float(rt60[1])
+    rmin, rmax = np.asarray(room_min, np.float64), np.asarray(room_max, np.float64)
+    margin, min_dist = float(wall_margin), float(min_dist)
+    if count < 1 or not 0 < lo <= hi:
+        raise ValueError('draw_rooms: count >= 1 and 0 < rt60[0] <= rt60[1] expected')
+    if rmin.shape != (3,) or rmax.shape != (3,) or np.any(rmin > rmax) or margin <= 0:
+        raise ValueError('draw_rooms: room_min <= room_max (three sides each) and a positive '
+                         'wall_margin expected')
+    inner = rmin - 2.0 * margin
+    if np.any(inner <= 0) or min_dist <= 0 or np.sqrt(np.sum(inner ** 2)) < 2.0 * min_dist:
+        raise ValueError('draw_rooms: the smallest room leaves no space for a source and a '
+                         'receiver {} m apart, {} m from the walls'.format(min_dist, margin))
+    out = dict(room=np.zeros((count, 3)), src=np.zeros((count, 3)), mic=np.zeros((count, 3)),
+               rt60=np.zeros(count))
+    for i in range(count):
+        out['rt60'][i] = rng.uniform(lo, hi)
+        room = rng.uniform(rmin, rmax)
+        while True:
+            src = rng.uniform(margin, room - margin)
+            mic = rng.uniform(margin, room - margin)
+            if np.sqrt(np.sum((src - mic) ** 2)) >= min_dist:
+                break
+        out['room'][i], out['src'][i], out['mic'][i] = room, src, mic
+    out['beta'] = np.repeat(beta_from_rt60(out['room'], out['rt60'])[:, None], 6, axis=1)
+    return out
+
+
 class RIRBank(object):
     """Room impulse responses, normalised once on the host in float64: each is cut to `max_taps`,
     d = argmax |h| (first occurrence) is its direct path, h / h[d] is rounded to fp32 once — the
@@ -293,6 +348,29 @@ class RIRBank(object):
             wavs, _ = resample_many(wavs, [r for r, _ in read], target_rate, resample_zeros,
                                     resample_beta)
         return cls(wavs, files=names, max_taps=max_taps)
+
+    @classmethod
+    def synthetic(cls, count, seed, device, max_taps=16384, srate=16000, **draw):
+        """A bank of `count` image-source responses of rooms drawn by `draw_rooms` (its keyword
+        arguments in `draw`) from numpy.random.default_rng(seed), synthesised on `device` (a HIP
+        device) at `srate`: row i is ceil(1.5 rt60_i srate) taps long, `max_taps` at the most.  The
+        rows go through the constructor like any others; `rooms` keeps what `draw_rooms` gave."""
+        device = torch.device(device)
+        if device.type != 'cuda':
+            raise RuntimeError('RIRBank: segan_pytorch_amd runs only on an MI355X (HIP) device; '
+                               'there is no CPU path')
+        max_taps = int(max_taps)
+        if max_taps < 1:
+            raise ValueError('RIRBank: max_taps must be positive, got {}'.format(max_taps))
+        rooms = draw_rooms(np.random.default_rng(seed), count, **draw)
+        lengths = np.minimum(max_taps, np.ceil(1.5 * rooms['rt60'] * srate)).astype(np.int64)
+        with torch.cuda.device(device):
+            h = ops.rir_shoebox(rooms['room'], rooms['src'], rooms['mic'], rooms['beta'],
+                                int(lengths.max()), srate=srate, lengths=lengths).cpu().numpy()
+        bank = cls([h[i, :n] for i, n in enumerate(lengths)],
+                   files=['synthetic{}'.format(i) for i in range(len(lengths))], max_taps=max_taps)
+        bank.rooms = rooms
+        return bank
 
     def __len__(self):
         return len(self.rirs)

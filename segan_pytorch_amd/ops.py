@@ -1831,6 +1831,106 @@ def omlsa_rows(x, lengths=None, srate=16000, out_dtype=None, ws_cap=OMLSA_WS_CAP
     return _omlsa_run(x, lengths, srate, out_dtype, ws_cap, False)['y']
 
 
+_R = _lib.RIR_DEFINES  # the integer macros of include/segan_rir.h
+RIR_TILE = _R['SEGAN_RIR_TILE']      # samples per workgroup
+RIR_GEOM = _R['SEGAN_RIR_GEOM']      # doubles per room: L, s, r, beta
+RIR_MAX_T = _R['SEGAN_RIR_MAX_T']
+RIR_RATES = (16000, 8000)
+RIR_C = 343.0                        # m/s
+
+
+def rir_dims(count, T, srate=16000):
+    """segan_rir_dims (host only) as a dict: half_width (Hw = srate / 250), stride (entries per
+    wall of the power tables), tiles of a row of T samples, ws_bytes for `count` responses."""
+    dims = (ctypes.c_int64 * 4)()
+    check(_lib.load().segan_rir_dims(count, T, srate, dims), 'rir')
+    return dict(zip(('half_width', 'stride', 'tiles', 'ws_bytes'), list(dims)))
+
+
+def rir_tables(beta, n_max):
+    """The powers of the reflection coefficients, built on the host: beta [count, 6] or [6] ->
+    numpy fp64 [count, 6, n_max + 1] with tab[.., 0] = 1 and tab[.., i] = tab[.., i - 1] * beta,
+    one rounding per entry (0^0 = 1).  The oracle and the device read these bits."""
+    import numpy as np
+    beta = np.asarray(beta, np.float64).reshape(-1, 6)
+    n_max = _int_arg(n_max, 'rir: n_max', 0, 1 << 24)
+    tab = np.ones(beta.shape + (n_max + 1,), np.float64)
+    for i in range(1, n_max + 1):
+        tab[..., i] = tab[..., i - 1] * beta
+    return tab
+
+
+def _rir_geom(room, src, mic, beta):
+    """room, src, mic [count, 3] or [3] and beta [count, 6] or [6] (a single row is repeated) as
+    numpy fp64 [count, 15]; the library checks the values."""
+    import numpy as np
+    parts = []
+    for name, v, w in (('room', room, 3), ('src', src, 3), ('mic', mic, 3), ('beta', beta, 6)):
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu().numpy()
+        a = np.asarray(v, np.float64)
+        if a.ndim not in (1, 2) or a.shape[-1] != w or a.size == 0:
+            raise ValueError('rir: {} must be [count, {}] or [{}], got {}'.format(
+                name, w, w, a.shape))
+        parts.append(a.reshape(-1, w))
+    count = max(len(a) for a in parts)
+    for i, a in enumerate(parts):
+        if len(a) not in (1, count):
+            raise ValueError('rir: room, src, mic and beta must agree on count, got {}'.format(
+                [len(p) for p in parts]))
+        parts[i] = np.broadcast_to(a, (count, a.shape[1]))
+    return np.ascontiguousarray(np.concatenate(parts, axis=1))
+
+
+def _rir_run(room, src, mic, beta, taps, srate, lengths, stages):
+    geom = _rir_geom(room, src, mic, beta)
+    count = len(geom)
+    T = _int_arg(taps, 'rir: taps', 1, RIR_MAX_T)
+    if isinstance(srate, bool) or srate not in RIR_RATES:
+        raise ValueError('rir: srate must be one of {}, got {!r}'.format(RIR_RATES, srate))
+    if not 1 <= count <= 65535:
+        raise ValueError('rir: 1 .. 65535 rooms, got {}'.format(count))
+    if not torch.cuda.is_available():
+        raise RuntimeError('rir: segan_pytorch_amd runs only on an MI355X (HIP) device; there is '
+                           'no CPU path')
+    device = torch.device('cuda', torch.cuda.current_device())
+    lens = None if lengths is None else _row_lengths('rir', lengths, count, T, device)
+    lib = _lib.load()
+    d = rir_dims(count, T, srate)
+    tables = torch.from_numpy(rir_tables(geom[:, 9:15], d['stride'] - 1)).to(device)
+    ws = _stream_scratch(d['ws_bytes'] + 8, device)
+    ws = ws[(-ws.data_ptr()) % 8:]
+    h = torch.empty((count, T), device=device, dtype=torch.float64)
+    images = torch.empty(count, device=device, dtype=torch.int64) if stages else None
+    check(lib.segan_rir(geom.ctypes.data_as(ctypes.c_void_p), _ptr(tables), _ptr(lens), count, T,
+                        srate, _ptr(h), _ptr(images), _ptr(ws), _stream()), 'rir')
+    out = {'h': h}
+    if stages:
+        out['images'], out['geom'], out['tables'] = images, geom, tables
+    return out
+
+
+def rir_stages(room, src, mic, beta, taps, srate=16000, lengths=None):
+    """`rir_shoebox` with what it rests on, as a dict: 'h' [count, taps] (fp64, device), 'images'
+    [count] (int64, device: the images that reach each row, whatever their amplitude), 'geom'
+    (numpy fp64 [count, 15]: L, s, r, beta as the library received them) and 'tables' (fp64 device
+    [count, 6, stride]: `rir_tables`)."""
+    return _rir_run(room, src, mic, beta, taps, srate, lengths, True)
+
+
+def rir_shoebox(room, src, mic, beta, taps, srate=16000, lengths=None):
+    """Room impulse responses of shoebox rooms by the image-source method (Allen & Berkley 1979,
+    fractional delays by Peterson's Hann-windowed sinc of 8 ms) on the device, all arithmetic fp64;
+    the definition is scripts/rir_oracle.py.  room [count, 3] (metres, 1 ..
+    50 per axis), src and mic [count, 3] (strictly inside, at least 0.05 m apart), beta [count, 6]
+    (reflection coefficients in 0 .. 1 of the walls x = 0, x = Lx, y = 0, y = Ly, z = 0, z = Lz);
+    host arrays, a single row is repeated.  Returns fp64 [count, taps] on the current device with
+    the physical scale 1 / (4 pi d); row i is zero from lengths[i] on (host integers 0 .. taps).
+    c = 343 m/s; no high-pass, no directivity, no air absorption.  Fixed operation order: a row's
+    bits depend neither on the other rows, nor on taps, nor on lengths beyond the masking."""
+    return _rir_run(room, src, mic, beta, taps, srate, lengths, False)['h']
+
+
 _E = _lib.EXT_DEFINES   # the integer macros of include/segan_dereverb.h
 WPE_RATES = (8000, 16000)
 WPE_MAX_T = 1 << 24

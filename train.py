@@ -12,7 +12,9 @@ batches are normalised / pre-emphasised on the GPU (with `--additive_noises DIR`
 into them on the fly at `--additive_snrs` dB, the reference's Additive; with `--reverb_rirs DIR`
 each selected clean slice is first convolved on the GPU with a room impulse response drawn from
 DIR's wavs: `--reverb_prob` is the share of items selected, `--reverb_max_taps` cuts the
-responses, `--reverb_resample` converts responses that are not 16 kHz; with `--distort KIND ...`
+responses, `--reverb_resample` converts responses that are not 16 kHz, and `--reverb_synth N` synthesises
+N responses of shoebox rooms on the GPU instead of, or after, DIR's: `--reverb_rt60 LO HI`,
+`--reverb_room_min X Y Z` and `--reverb_room_max X Y Z` bound the rooms drawn; with `--distort KIND ...`
 each selected item (`--distort_prob`) is then clipped, has chunks of speech removed or is band
 limited on the GPU, one kind per item drawn from `clip chop bandlimit`: `--clip_factors`,
 `--chop_max`, `--chop_durs LO HI` and `--bandlimit_cutoffs` set the kinds' parameters, and
@@ -54,6 +56,11 @@ DISTORT_MAX_K = 2048        # ops.FIR_MAX_K
 WHISPER_TILTS = (0.0, 0.5, 0.9)
 WHISPER_LAG_HZ = 120.0
 WHISPER_MAX_LAG_HZ = 1000.0
+# the defaults of --reverb_synth (augment.draw_rooms)
+REVERB_RT60 = (0.2, 0.8)
+REVERB_ROOM_MIN = (3.0, 3.0, 2.5)
+REVERB_ROOM_MAX = (10.0, 8.0, 4.0)
+REVERB_ROOM_SMALLEST = 2.0  # metres: source and receiver keep 0.5 m from every wall
 
 # (flag, kwargs) — names and defaults are the reference's (train.py:101-247)
 FLAGS = [
@@ -209,6 +216,22 @@ FLAGS = [
                                help='with --reverb_rirs: convert responses that are not 16 kHz to '
                                     '16 kHz on the GPU when they are read; without it their rate '
                                     'is ignored')),
+    ('--reverb_synth', dict(type=int, default=0, metavar='N',
+                            help='with --pcm_shard: N room impulse responses of shoebox rooms are '
+                                 'synthesised on the GPU by the image-source method when training '
+                                 'starts (the same on every rank, from --seed) and used like the '
+                                 'responses of --reverb_rirs, after them when both are given; no '
+                                 'measured response is needed')),
+    ('--reverb_rt60', dict(type=float, nargs=2, default=list(REVERB_RT60), metavar=('LO', 'HI'),
+                           help='with --reverb_synth: the nominal reverberation time of a room is '
+                                'drawn uniformly in LO .. HI seconds (Sabine; the synthesised '
+                                'response decays 1.2 to 1.4 times more slowly)')),
+    ('--reverb_room_min', dict(type=float, nargs=3, default=list(REVERB_ROOM_MIN),
+                               metavar=('X', 'Y', 'Z'),
+                               help='with --reverb_synth: the smallest room in metres')),
+    ('--reverb_room_max', dict(type=float, nargs=3, default=list(REVERB_ROOM_MAX),
+                               metavar=('X', 'Y', 'Z'),
+                               help='with --reverb_synth: the largest room in metres')),
     ('--distort', dict(type=str, nargs='+', default=None, choices=list(DISTORT_KINDS),
                        metavar='KIND',
                        help='with --pcm_shard: the signal-level distortions (clip chop bandlimit) '
@@ -297,7 +320,21 @@ def check_reverb_flags(opts):
     rirs = getattr(opts, 'reverb_rirs', None)
     prob = getattr(opts, 'reverb_prob', 1.0)
     max_taps = getattr(opts, 'reverb_max_taps', 16384)
-    if not _stage_on(opts, rirs is not None, '--reverb_rirs', 'reverberates', (
+    synth = getattr(opts, 'reverb_synth', 0)
+    rt60 = list(getattr(opts, 'reverb_rt60', REVERB_RT60))
+    room_min = list(getattr(opts, 'reverb_room_min', REVERB_ROOM_MIN))
+    room_max = list(getattr(opts, 'reverb_room_max', REVERB_ROOM_MAX))
+    if synth < 0:
+        raise SystemExit('--reverb_synth must not be negative, got {}'.format(synth))
+    _refuse_orphans(((synth == 0 and (rt60 != list(REVERB_RT60) or room_min != list(REVERB_ROOM_MIN)
+                                      or room_max != list(REVERB_ROOM_MAX)),
+                      '--reverb_rt60 / --reverb_room_min / --reverb_room_max need '
+                      '--reverb_synth N'),))
+    if synth > 0 and rirs is None:
+        if getattr(opts, 'reverb_resample', False):
+            raise SystemExit('--reverb_resample needs --reverb_rirs DIR')
+        _needs_pcm_shard(opts, '--reverb_synth', 'reverberates')
+    elif not _stage_on(opts, rirs is not None, '--reverb_rirs', 'reverberates', (
             (prob != 1.0 or max_taps != 16384,
              '--reverb_prob / --reverb_max_taps need --reverb_rirs DIR'),
             (getattr(opts, 'reverb_resample', False),
@@ -306,6 +343,13 @@ def check_reverb_flags(opts):
     _prob_in_range('--reverb_prob', prob)
     if max_taps < 1:
         raise SystemExit('--reverb_max_taps must be positive, got {}'.format(max_taps))
+    if synth > 0:
+        if not 0.0 < rt60[0] <= rt60[1]:
+            raise SystemExit('--reverb_rt60 needs 0 < LO <= HI, got {}'.format(rt60))
+        if not all(REVERB_ROOM_SMALLEST <= a <= b <= 50.0 for a, b in zip(room_min, room_max)):
+            raise SystemExit('--reverb_room_min / --reverb_room_max need {} <= min <= max <= 50 '
+                             'metres per side, got {} and {}'.format(REVERB_ROOM_SMALLEST,
+                                                                     room_min, room_max))
     return True
 
 
@@ -452,9 +496,23 @@ def main(opts):
                                 target_rate=16000 if opts.additive_resample else None)
         reverb = None
         if use_reverb:
-            from segan_pytorch_amd.augment import Reverb
-            reverb = Reverb(opts.reverb_rirs, max_taps=opts.reverb_max_taps,
-                            target_rate=16000 if opts.reverb_resample else None)
+            from segan_pytorch_amd.augment import Reverb, RIRBank
+            if opts.reverb_rirs is not None:
+                reverb = Reverb(opts.reverb_rirs, max_taps=opts.reverb_max_taps,
+                                target_rate=16000 if opts.reverb_resample else None)
+            if opts.reverb_synth > 0:
+                # opts.seed, not seed + rank: every rank trains on the same rooms
+                bank = RIRBank.synthetic(opts.reverb_synth, opts.seed, device,
+                                         max_taps=opts.reverb_max_taps, rt60=opts.reverb_rt60,
+                                         room_min=opts.reverb_room_min,
+                                         room_max=opts.reverb_room_max)
+                if reverb is not None:    # the responses of the files come first
+                    files = reverb.bank
+                    merged = RIRBank(files.rirs + bank.rirs, files=files.files + bank.files,
+                                     max_taps=opts.reverb_max_taps)
+                    merged.rooms = bank.rooms
+                    bank = merged
+                reverb = Reverb(bank)
         distort = None
         if use_distort:
             from segan_pytorch_amd import augment
