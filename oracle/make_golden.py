@@ -49,6 +49,18 @@ tiny_wsegan_interf.pt (python oracle/make_golden.py interf) the literal ``WSEGAN
                  --misalign_pair --interf_pair (four D forwards per step, d_weight 1/4),
                  'interf_only' = --interf_pair alone (three forwards, still weighted 1/4 as the
                  reference does).
+tiny_epochs.pt   (python oracle/make_golden.py epochs; with tiny_epochs_d / _mid_d / _mid_dsq / _s2.pt,
+                 which hold its large tensors so that no file exceeds 1 MiB) the literal
+                 ``SEGAN.train`` over several epochs of a shuffling DataLoader that ends every epoch
+                 on a short batch, log_freq=1: 'decay_clamp' = the tiny net, batches 3, 3, 1, five
+                 epochs, l1_dec_epoch=2, l1_dec_step=15 (weight 100, 85 ... 10, clamped to 0 at
+                 iteration 10; five saves through the max_ckpts=3 savers); 's2_mse' = the stride-2
+                 net with --reg_loss mse_loss, batches 2, 2, 1, three epochs, the shipped 1e-5 step
+                 from the first batch on.  Per iteration: items, z, phase shifts, L1 weight, the four
+                 logged losses; final weights; directory listing and index files; RNG marks after the
+                 run; the epoch-3 checkpoints of 'decay_clamp'; and `gaps`, the distance of this
+                 float32 run from the same run on the oracle in float64 (asserted <= STEP_TOL / 4;
+                 the float32 oracle replay is asserted bit-equal).
 """
 import json
 import os
@@ -517,10 +529,282 @@ def make_corners(ref):
     print('tiny_corners.pt done')
 
 
+def tiny_s2_opts():
+    """The stride-2 (vanilla-SEGAN style) tiny net of tiny_s2.pt."""
+    o2 = tiny_opts()
+    o2.update(dict(genc_fmaps=[4, 8, 8, 16], denc_fmaps=[4, 8, 8, 16], genc_poolings=[2] * 4,
+                   denc_poolings=[2] * 4, z_dim=16, dpool_slen=16, slice_size=256))
+    return o2
+
+
+# ---------------- tiny_epochs: the literal SEGAN.train over several epochs ----------------
+STEP_TOL = 5e-5                     # tests/test_gpu_model.py: 10 % of one RMSprop step
+NOISE_KEYS = ('conv.bias', 'norm.running_mean')
+LOSS_TAGS = ('D_real', 'D_fake', 'G_adv', 'G_l1')
+MID_STEP = 10                       # weights_EOE_*-10.ckpt: the state after iteration 9
+
+EPOCH_FLAVOURS = {
+    # weight 100 in epoch 1, 85 ... 10 over epochs 2-3, clamped to 0 at iteration 10 and held there;
+    # five end-of-epoch saves through a max_ckpts=3 Saver
+    'decay_clamp': dict(opts=tiny_opts, extra={}, n=7, T=1024, batch_size=3, epoch=5,
+                        l1_weight=100, l1_dec_epoch=2, l1_dec_step=15, data_seed=61, run_seed=67,
+                        mid=True),
+    # the shipped default step from the first batch on, stride-2 layers down to B = 1, MSE regression
+    's2_mse': dict(opts=tiny_s2_opts, extra={'reg_loss': 'mse_loss'}, n=5, T=256, batch_size=2,
+                   epoch=3, l1_weight=100, l1_dec_epoch=1, l1_dec_step=1e-5, data_seed=71,
+                   run_seed=73, mid=False),
+}
+
+
+class PairDataset(torch.utils.data.Dataset):
+    """Map-style dataset over synth(): item i is ('u<i>', clean[i], noisy[i], 0).  `served` logs the
+    indices in the order the loader asked for them."""
+
+    def __init__(self, clean, noisy):
+        self.clean, self.noisy, self.served = clean, noisy, []
+
+    def __len__(self):
+        return self.clean.size(0)
+
+    def __getitem__(self, i):
+        self.served.append(int(i))
+        return 'u{}'.format(int(i)), self.clean[i], self.noisy[i], 0
+
+
+class ScalarLog(object):
+    """Stands in for SummaryWriter: keeps the add_scalar calls."""
+    last = None
+
+    def __init__(self, *a, **k):
+        self.scalars = []
+        ScalarLog.last = self
+
+    def add_scalar(self, tag, value, step):
+        self.scalars.append((tag, float(value), int(step)))
+
+    def add_histogram(self, *a, **k):
+        pass
+
+    def series(self, tag):
+        return [v for t, v, _ in self.scalars if t == tag]
+
+
+def _train_frame_local(name):
+    """The value of local `name` in the innermost running frame of a function called `train`."""
+    f = sys._getframe(1)
+    while f is not None:
+        if f.f_code.co_name == 'train' and name in f.f_locals:
+            return f.f_locals[name]
+        f = f.f_back
+    raise RuntimeError('no train frame with a local {}'.format(name))
+
+
+def _replay_epochs(fx, dtype):
+    """The recorded batches, z, rolls and L1 weights through oracle.gan_step in `dtype`, RMSprop
+    state carried from step to step."""
+    sys.path.insert(0, os.path.join(HERE, '..', 'tests'))
+    from conftest import oracle_kwargs
+    import segan_oracle as O
+    o = fx['opts']
+    cast = lambda t: t.to(dtype) if torch.is_floating_point(t) else t.clone()
+    G = {k: cast(v) for k, v in fx['G0'].items()}
+    D = {k: cast(v) for k, v in fx['D0'].items()}
+    g_sq = d_sq = None
+    out = {'losses': {t: [] for t in LOSS_TAGS}}
+    for i, idx in enumerate(fx['order']):
+        clean = fx['clean'][idx].unsqueeze(1).to(dtype)
+        noisy = fx['noisy'][idx].unsqueeze(1).to(dtype)
+        res = O.gan_step(G, D, clean, noisy, fx['z'][i].to(dtype), fx['rolls'][i],
+                         o['genc_poolings'], l1_weight=fx['l1_weights'][i], lr=o['g_lr'],
+                         g_sq=g_sq, d_sq=d_sq, **oracle_kwargs(o))
+        G, D, g_sq, d_sq = res['G'], res['D'], res['g_sq'], res['d_sq']
+        for t, k in zip(LOSS_TAGS, ('d_real_loss', 'd_fake_loss', 'g_adv_loss', 'g_l1_loss')):
+            out['losses'][t].append(float(res[k]))
+        if i + 2 == MID_STEP:
+            out['mid'] = {'G': {k: v.clone() for k, v in G.items()},
+                          'D': {k: v.clone() for k, v in D.items()},
+                          'g_sq': {k: v.clone() for k, v in g_sq.items()},
+                          'd_sq': {k: v.clone() for k, v in d_sq.items()}}
+    out['G'], out['D'] = G, D
+    return out
+
+
+def _max_rel(a, b):
+    den = b.abs().max().item()
+    return (a.double() - b.double()).abs().max().item() / (den if den > 0 else 1.0)
+
+
+def _epochs_flavour(ref, name, spec):
+    import tempfile
+    sys.path.insert(0, os.path.join(HERE, '..', 'tests'))
+    from conftest import draw_rolls
+    ref_model = sys.modules[ref.SEGAN.__module__]
+    o = spec['opts']()
+    o.update(spec['extra'])
+    o.update({k: spec[k] for k in ('batch_size', 'epoch', 'l1_weight', 'l1_dec_epoch', 'l1_dec_step')})
+    seed_all(111)
+    segan = ref.SEGAN(SimpleNamespace(**o))
+    fx = {'opts': o, 'G0': clone_sd(segan.G), 'D0': clone_sd(segan.D), 'run_seed': spec['run_seed']}
+    fx['clean'], fx['noisy'] = synth(spec['n'], spec['T'], spec['data_seed'])
+    ds = PairDataset(fx['clean'], fx['noisy'])
+    loader = torch.utils.data.DataLoader(ds, batch_size=o['batch_size'], shuffle=True, num_workers=0)
+    g_calls, d_calls = [], []
+
+    def g_hook(mod, args):
+        g_calls.append((torch.get_rng_state(), args[0].detach().clone(),
+                        _train_frame_local('l1_weight')))
+
+    def d_hook(mod, args):
+        d_calls.append((random.getstate(), args[0].detach().clone()))
+
+    hooks = [segan.G.register_forward_pre_hook(g_hook), segan.D.register_forward_pre_hook(d_hook)]
+    _writer = ref_model.SummaryWriter
+    ref_model.SummaryWriter = ScalarLog
+    try:
+        with tempfile.TemporaryDirectory() as tmp:
+            oo = dict(o)
+            oo['save_path'] = tmp
+            segan.save_path = tmp
+            seed_all(spec['run_seed'])
+            segan.train(SimpleNamespace(**oo), loader, nn.MSELoss(), o['l1_weight'], o['l1_dec_step'],
+                        o['l1_dec_epoch'], 1, va_dloader=None, device='cpu')
+            fx['rand4'], fx['random'] = torch.rand(4), random.random()
+            fx['listing'] = sorted(os.listdir(tmp))
+            fx['index'] = {}
+            for p in ('EOE_G-', 'EOE_D-'):
+                with open(os.path.join(tmp, p + 'checkpoints')) as f:
+                    fx['index'][p] = json.load(f)
+            if spec['mid']:
+                for net, p, cls in ((segan.G, 'EOE_G-', 'Generator'), (segan.D, 'EOE_D-', 'Discriminator')):
+                    ck = torch.load(os.path.join(tmp, 'weights_{}{}-{}.ckpt'.format(p, cls, MID_STEP)),
+                                    weights_only=False)
+                    assert ck['step'] == MID_STEP
+                    names = [k for k, q in net.named_parameters() if q.requires_grad]
+                    st = ck['optimizer']['state']
+                    fx['mid_' + cls[0]] = {k: v.clone() for k, v in ck['state_dict'].items()}
+                    fx['mid_' + cls[0] + '_sq'] = {k: st[i]['square_avg'].clone() for i, k in enumerate(names)}
+    finally:
+        ref_model.SummaryWriter = _writer
+        for h in hooks:
+            h.remove()
+    n_it = len(g_calls)
+    assert len(d_calls) == 3 * n_it
+    fx['G_final'], fx['D_final'] = clone_sd(segan.G), clone_sd(segan.D)
+    fx['losses'] = {t: ScalarLog.last.series(t) for t in LOSS_TAGS}
+    assert all(len(v) == n_it for v in fx['losses'].values())
+    fx['batch_sizes'] = [c[1].size(0) for c in g_calls]
+    fx['l1_weights'] = [float(c[2]) for c in g_calls]
+    # the schedule in plain python (model.py:272-276), as a cross-check of the frame read
+    w, it, want = o['l1_weight'], iter(fx['l1_weights']), []
+    for ep in range(1, o['epoch'] + 1):
+        for _ in range(len(loader)):
+            if ep >= o['l1_dec_epoch'] and w > 0:
+                w = max(0, w - o['l1_dec_step'])
+            want.append(float(w))
+    assert want == fx['l1_weights'], (want, fx['l1_weights'])
+    served, fx['order'] = list(ds.served), []
+    for b in fx['batch_sizes']:
+        fx['order'].append(served[:b])
+        served = served[b:]
+    assert not served
+    fx['z'], fx['rolls'] = [], []
+    save_t, save_r = torch.get_rng_state(), random.getstate()
+    zl = o['slice_size']
+    for p in o['genc_poolings']:
+        zl //= p
+    for i, (rng, noisy, _) in enumerate(g_calls):
+        assert torch.equal(noisy[:, 0], fx['noisy'][fx['order'][i]])
+        assert torch.equal(d_calls[3 * i][1][:, 0], fx['clean'][fx['order'][i]])
+        torch.set_rng_state(rng)
+        fx['z'].append(torch.randn(noisy.size(0), o['z_dim'], zl))
+        random.setstate(d_calls[3 * i][0])
+        fx['rolls'].append([draw_rolls(len(o['denc_poolings']), o['phase_shift']) for _ in range(3)])
+    torch.set_rng_state(save_t)
+    random.setstate(save_r)
+    # ---- the reference's own rounding: the same run on the oracle in float32 and in float64 ----
+    r32, r64 = _replay_epochs(fx, torch.float32), _replay_epochs(fx, torch.float64)
+    # (floating tensors: the oracle keeps no num_batches_tracked counter)
+    for net in 'GD':
+        for k, v in fx[net + '_final'].items():
+            assert not torch.is_floating_point(v) or torch.equal(r32[net][k], v), (net, 'fp32 replay', k)
+    gaps = {'G': {}, 'D': {}, 'losses': {}}
+    for net in 'GD':
+        for k, v in fx[net + '_final'].items():
+            if torch.is_floating_point(v) and not (net == 'D' and k.endswith(NOISE_KEYS)):
+                gaps[net][k] = (v.double() - r64[net][k]).abs().max().item()
+    for t in LOSS_TAGS:
+        gaps['losses'][t] = [abs(a - b) for a, b in zip(fx['losses'][t], r64['losses'][t])]
+    if spec['mid']:
+        for net, sq in (('G', 'g_sq'), ('D', 'd_sq')):
+            for k, v in fx['mid_' + net].items():
+                assert not torch.is_floating_point(v) or torch.equal(r32['mid'][net][k], v), ('mid', net, k)
+            gaps[net + '_sq'] = {k: _max_rel(v, r64['mid'][sq][k]) for k, v in fx['mid_' + net + '_sq'].items()
+                                 if not (net == 'D' and k.endswith(NOISE_KEYS))}
+    fx['gaps'] = gaps
+    worst = {net: max(gaps[net].items(), key=lambda kv: kv[1]) for net in 'GD'}
+    print('epochs', name, 'batches', fx['batch_sizes'], 'weights', fx['l1_weights'])
+    print('epochs', name, 'listing', fx['listing'])
+    print('epochs', name, 'reference fp32 vs oracle fp64, worst weight gap: G {:.2e} ({}), D {:.2e} ({})'.format(
+        worst['G'][1], worst['G'][0], worst['D'][1], worst['D'][0]))
+    print('epochs', name, 'worst loss gap', {t: '{:.1e}'.format(max(v)) for t, v in gaps['losses'].items()})
+    if spec['mid']:
+        print('epochs', name, 'worst mid-run square_avg gap (max_rel): G {:.2e}, D {:.2e}'.format(
+            max(gaps['G_sq'].values()), max(gaps['D_sq'].values())))
+    for net in 'GD':
+        assert worst[net][1] <= STEP_TOL / 4, (name, net, worst[net])
+    o['save_path'] = '/tmp/segan_golden_ckpt'
+    return fx
+
+
+def make_epochs(ref):
+    """tiny_epochs.pt: the literal ``SEGAN.train`` over a shuffling DataLoader whose last batch is
+    short, for several epochs, in two flavours (EPOCH_FLAVOURS): per iteration the batch, z, phase
+    shifts, L1 weight and the four logged losses; final weights; the checkpoint directory; where
+    the RNG streams stand afterwards; for 'decay_clamp' the mid-run checkpoint; and `gaps`, the
+    distance of this float32 run from the same run on the oracle in float64."""
+    out = {name: _epochs_flavour(ref, name, spec) for name, spec in EPOCH_FLAVOURS.items()}
+    # G0 / D0 are the seed-111 initialisations other fixtures already hold: checked, not stored twice
+    for name, src in EPOCHS_INIT.items():
+        init = torch.load(os.path.join(OUT, src), weights_only=False)
+        for net in ('G0', 'D0'):
+            got = out[name].pop(net)
+            assert got.keys() == init[net].keys() and all(torch.equal(v, init[net][k]) for k, v in got.items())
+    # the discriminator's state dicts are 0.76 MB each: the large entries go to files of their own
+    # (EPOCHS_PARTS), so that no file exceeds 1 MiB; tests/epochs_cases.py puts them together again
+    total = 0
+    for fname, entries in EPOCHS_PARTS.items():
+        part = {(name, key): out[name].pop(key) for name, key in entries}
+        total += _save_small(part, fname)
+    total += _save_small(out, 'tiny_epochs.pt')
+    print('tiny_epochs*.pt done, {:.2f} MB in all'.format(total / 1e6))
+    assert total < 5e6
+
+
+EPOCHS_INIT = {'decay_clamp': 'tiny_train2.pt', 's2_mse': 'tiny_s2.pt'}
+EPOCHS_PARTS = {
+    'tiny_epochs_d.pt': [('decay_clamp', 'D_final')],
+    'tiny_epochs_mid_d.pt': [('decay_clamp', 'mid_D')],
+    'tiny_epochs_mid_dsq.pt': [('decay_clamp', 'mid_D_sq')],
+    'tiny_epochs_s2.pt': [('s2_mse', 'G_final'), ('s2_mse', 'D_final')],
+}
+
+
+def _save_small(obj, fname):
+    path = os.path.join(OUT, fname)
+    torch.save(obj, path)
+    size = os.path.getsize(path)
+    print('{}: {:.2f} MB'.format(fname, size / 1e6))
+    assert size <= 1 << 20, (fname, size)
+    return size
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     ref = ref_harness.import_reference()
     torch.set_num_threads(max(1, os.cpu_count() or 1))
+    if len(sys.argv) > 1 and sys.argv[1] == 'epochs':
+        make_epochs(ref)
+        return
     if len(sys.argv) > 1 and sys.argv[1] == 'corners':
         make_corners(ref)
         return
@@ -589,9 +873,7 @@ def main():
     print('tiny_train2.pt done')
 
     # ---------------- tiny_s2: stride-2 (vanilla SEGAN style) ----------------
-    o2 = tiny_opts()
-    o2.update(dict(genc_fmaps=[4, 8, 8, 16], denc_fmaps=[4, 8, 8, 16], genc_poolings=[2] * 4,
-                   denc_poolings=[2] * 4, z_dim=16, dpool_slen=16, slice_size=256))
+    o2 = tiny_s2_opts()
     seed_all(111)
     segan = ref.SEGAN(SimpleNamespace(**o2))
     clean, noisy = synth(2, 256, 3)

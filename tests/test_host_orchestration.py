@@ -597,3 +597,19 @@ def test_distributed_sampler_epochs_advance(tiny_wsegan2):
     m = WSEGAN(SimpleNamespace(**tiny_wsegan2['opts']))
     firsts = [tuple(m.sample_dloader(dl)[1][:, 0, 0].tolist()) for _ in range(4)]
     assert len(set(firsts)) > 1, firsts
+
+
+@pytest.mark.parametrize('name', ['decay_clamp', 's2_mse'])
+def test_epochs_literal_train(name, tmp_path, monkeypatch):
+    """SEGAN.train over several epochs of a shuffling DataLoader whose last batch is short, against
+    the reference's literal loop (tests/epochs_cases.py: bars and flavours): the decaying and
+    clamped L1 weight, B = 3 -> 1 -> 3, the RNG streams across the epoch ends, the four logged
+    losses of every iteration, every final weight, the rotated end-of-epoch checkpoints."""
+    import epochs_cases as E
+    fx = E.load_epochs()[name]
+    m, rec = E.run_train(fx, tmp_path, monkeypatch, 'cpu')
+    E.check_run(name, fx, m, rec, tmp_path, 'emulated kernels')
+    if name == 'decay_clamp':
+        names = sorted(n for n in fx['listing'] if n.startswith('weights_EOE_G-'))
+        assert names == ['weights_EOE_G-Generator-{}.ckpt'.format(s) for s in (10, 13, 16, 7)]
+        E.check_mid_checkpoint(fx, m, tmp_path, 'emulated kernels')

@@ -398,3 +398,25 @@ def test_gate_hook_with_own_gates_is_the_identity(tiny_step):
     gd['h_1'][0, 0, 0] = ~gd['h_1'][0, 0, 0]
     _, _, _, _, gr3 = run(gg, gd)
     assert any(a is not None and not torch.equal(a, b) for a, b in zip(gr, gr3))
+
+
+@pytest.mark.parametrize('name', ['decay_clamp', 's2_mse'])
+def test_epochs_literal_train_replay(name):
+    """The reference's literal multi-epoch SEGAN.train (tests/epochs_cases.py) replayed on the
+    float32 oracle from the recorded batches, z, phase shifts and L1 weights (B = 3, 3, 1 per
+    epoch; the weight decaying to 0).  On the machine that made the fixture the replay is bit-equal
+    (asserted by oracle/make_golden.py epochs); elsewhere the convolutions may sum in another order,
+    so it is held to STEP_TOL / 4 — the figure the fixture's own float32-vs-float64 distance is
+    asserted to stay under — and the losses to the bars of the other replays."""
+    import epochs_cases as E
+    fx = E.load_epochs()[name]
+    G, D, losses = E.replay_on_oracle(fx)
+    g, gk = E.weight_distance(G, {k: v for k, v in fx['G_final'].items() if torch.is_floating_point(v)})
+    d, dk = E.weight_distance(D, {k: v for k, v in fx['D_final'].items() if torch.is_floating_point(v)},
+                              skip=E.NOISE_KEYS)
+    print('fp32 oracle replay {}: G {:.2e} ({}), D {:.2e} ({})'.format(name, g, gk, d, dk))
+    assert g <= E.STEP_TOL / 4 and d <= E.STEP_TOL / 4
+    for t in E.LOSS_TAGS:
+        for i, (a, v) in enumerate(zip(losses[t], fx['losses'][t])):
+            assert abs(a - v) <= max(E.ACT_TOL * max(1.0, abs(v)), 4 * fx['gaps']['losses'][t][i]), (t, i + 1)
+    assert all(losses['G_l1'][i] == 0.0 for i, w in enumerate(fx['l1_weights']) if w == 0)
